@@ -7,7 +7,16 @@ semantics of the reference (results independent of K).  With N ranks every rank 
 replica tree on its own GPU (seed 42 + rank): weak scaling, `value` = all ranks' iterations / the
 slowest rank's time.
 
-Sub-results on the same line (the rows of SURVEY.md §8d the driver would not see otherwise):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what that figure needs and no more:
+it grows the tree, warms up, times the N steps and prints the line.  `--dump-outputs DIR` also
+writes the tree as the timed steps left it (DIR/x.npy, y.npy, yaw.npy, parent.npy, float64); the
+scene and the sampling stream are seeded, so two builds can be compared array for array.
+`ms_per_step` is the timed region / N; the tree grows with every step and the exact nearest
+neighbour is a scan of it, so a step costs more the more steps precede it.
+
+Everything else runs with `--full` only: the CPU baselines, the size sweep, the profiled passes
+behind the rooflines and kernel chains, and these sub-results on the same line (the rows of
+SURVEY.md §8d the driver would not see otherwise):
   config3          8192 independent queries sharded contiguously over the N ranks (strong
                    scaling), one all_gather of per-query records over RCCL (nccl) when every rank
                    has its own GPU; `records_digest` is the same at every N when the sharded run
@@ -37,6 +46,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -74,8 +84,9 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without WORLD_SIZE the bench starts them itself")
     ap.add_argument("--workload", choices=WORKLOADS, default="default",
-                    help="default: config 2 + the sub-results; config2/config4/polygons: one tree, "
-                         "K-candidate windows (config4: 512x512 occupancy grid; polygons: "
+                    help="default: config 2 (with --full + the sub-results); "
+                         "config2/config4/polygons: one tree, K-candidate windows "
+                         "(config4: 512x512 occupancy grid; polygons: "
                          "create_circle polygons, SURVEY §8f row 3); config3: independent queries "
                          "sharded over the ranks; config5: RRT* query batch; config1 / "
                          "config1_polygons: the reference's bench scene; plan / example_rrt: "
@@ -104,7 +115,22 @@ def parse(argv=None):
                     help="where the full record goes (stdout gets the compact line)")
     ap.add_argument("--allow-variant-lib", action="store_true",
                     help="accept PP_AMD_LIB pointing at another build (experiments only)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the sub-results of the default "
+                         "workload, the CPU baselines, the size sweep and the profiled passes "
+                         "(rooflines, kernel chains); --no-sub / --no-cpu-baseline / "
+                         "--no-size-sweep / --pmc-run take single parts out again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what they computed (the tree, or the "
+                         "batch's per-query state and a fixed sample of its trees) as "
+                         "DIR/<name>.npy in float64 (one-tree and batch workloads)")
+    args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload in ("config1", "config1_polygons", "plan",
+                                               "example_rrt"):
+        ap.error(f"--dump-outputs is not available for --workload {args.workload}")
+    return args
 
 
 # ------------------------------------------------------------------------------ ranks
@@ -452,27 +478,65 @@ def timed_windows(p, n_windows, window):
     return time.perf_counter() - t0
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_QUERIES = 64
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (node indices and counts are
+    exact there), at most DUMP_MAX_BYTES in all.  The inputs are seeded, so two builds given the
+    same arguments can be compared file for file."""
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed {DUMP_MAX_BYTES}")
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+
+
+def dump_batch(dirpath, batch, star):
+    """A query batch's outputs: every query's tree size and iteration count, and the trees of a
+    fixed seeded sample of DUMP_SAMPLE_QUERIES queries, one after another (`sample_offsets`
+    holds where each begins)."""
+    stt = batch.state()
+    n = stt[0]
+    rng = np.random.default_rng(0)
+    pick = np.sort(rng.choice(len(n), size=min(len(n), DUMP_SAMPLE_QUERIES), replace=False))
+    trees = [batch.tree(int(q), int(n[q])) for q in pick]
+    arrays = {"nodes": n, "iterations": stt[1], "sample_queries": pick,
+              "sample_offsets": np.concatenate([[0], np.cumsum([len(t[0]) for t in trees])])}
+    for i, name in enumerate(("x", "y", "yaw", "parent") + (("cost",) if star else ())):
+        arrays["sample_" + name] = np.concatenate([t[i] for t in trees])
+    if star:
+        arrays["rewires"] = stt[3]
+    dump_outputs(dirpath, arrays)
+
+
 TREE_TAG = {"config2": "", "config4": "_config4", "polygons": "_polygons"}
 
 
 def run_tree(args, D, raw, workload, with_cpu):
-    """Config 2 / 4 / polygons: grow a tree to args.nodes (untimed; windows at ~1k and ~10k nodes
-    timed on the way), W warmup windows, then `steps` windows timed back to back, then a profiled
-    pass of as many windows (HIP events around every kernel)."""
-    steps = args.steps or 20
+    """Config 2 / 4 / polygons: grow a tree to args.nodes (untimed), W warmup windows, then `steps`
+    windows timed back to back.  With --full: windows at ~1k and ~10k nodes timed on the way, and
+    after the timed region a profiled pass of as many windows (HIP events around every kernel)."""
+    steps = 20 if args.steps is None else args.steps
     p = make_planner(raw, args.seed + D.rank, args.window, D.device)
     sweep = {}
     marks = [] if args.no_size_sweep else [1_000, 10_000]
     while p.tree_size() < args.nodes:
         if marks and p.tree_size() >= marks[0]:
             m = marks.pop(0)
-            n0 = p.tree_size()
-            p.reset_stats()
-            dt = timed_windows(p, 5, args.window)
-            st = p.stats()
-            sweep[str(m)] = {"iterations_per_s": st["iterations"] / dt, "tree_nodes": n0,
-                             "ms_per_window": round(1e3 * dt / max(st["windows"], 1), 4),
-                             "stats": {k: st[k] for k in STAT_KEYS}}
+            if args.full:
+                n0 = p.tree_size()
+                p.reset_stats()
+                dt = timed_windows(p, 5, args.window)
+                st = p.stats()
+                sweep[str(m)] = {"iterations_per_s": st["iterations"] / dt, "tree_nodes": n0,
+                                 "ms_per_window": round(1e3 * dt / max(st["windows"], 1), 4),
+                                 "stats": {k: st[k] for k in STAT_KEYS}}
+            else:
+                p.extend(5 * args.window)  # the same growth as with --full, untimed
         p.extend(args.window)
     p.extend(args.warmup * args.window)
     p.synchronize()
@@ -492,21 +556,27 @@ def run_tree(args, D, raw, workload, with_cpu):
                               "tree_nodes": n_start,
                               "ms_per_window": round(1e3 * t_local / max(st["windows"], 1), 4),
                               "stats": {k: st[k] for k in STAT_KEYS}}
-    p.reset_stats()
-    p.set_profiling(True)
-    p.extend(steps * args.window)
-    p.synchronize()
-    p.set_profiling(False)
-    sp = p.stats()
-    tag = TREE_TAG[workload]
+    if args.dump_outputs and D.rank == 0:
+        x, y, yaw, par = p.tree()  # the tree as the timed steps left it
+        dump_outputs(args.dump_outputs, {"x": x, "y": y, "yaw": yaw, "parent": par})
     res = {
         "value": iters_total / t_max, "t_max": t_max, "steps": steps, "n_start": n_start,
         "node_evals_per_s_per_gpu": round(st["node_evals"] / t_local, 1),
         "sizes": sweep, "stats": {k: st[k] for k in STAT_KEYS},
-        "roofline": screen_roofline(sp, load_profile(f"window_kernel_pmc{tag}.json")),
-        "walk_roofline": walk_roofline(sp, load_profile(f"steer_walk_pmc{tag}.json"), workload),
-        "window_chain_us": window_chain(sp),
+        "roofline": None, "walk_roofline": None, "window_chain_us": None,
     }
+    if args.full:
+        p.reset_stats()
+        p.set_profiling(True)
+        p.extend(steps * args.window)
+        p.synchronize()
+        p.set_profiling(False)
+        sp = p.stats()
+        tag = TREE_TAG[workload]
+        res["roofline"] = screen_roofline(sp, load_profile(f"window_kernel_pmc{tag}.json"))
+        res["walk_roofline"] = walk_roofline(sp, load_profile(f"steer_walk_pmc{tag}.json"),
+                                             workload)
+        res["window_chain_us"] = window_chain(sp)
     if with_cpu:
         res["cpu_baseline"] = cpu_baseline_tree(raw, p, args)
     p.close()
@@ -582,7 +652,8 @@ def run_batch(args, D, star, with_cpu):
     """Config 3 (star=False) / config 5 (star=True): args.queries independent planners, sharded
     contiguously over the ranks; a step = one lockstep iteration of every query of the rank; the
     timed region is the whole max_iter-step run of a fresh batch after an untimed warmup batch;
-    then a profiled pass of the same run, on the same streams (HIP events around every kernel)."""
+    then, with --full, a profiled pass of the same run, on the same streams (HIP events around
+    every kernel)."""
     from pathplanning_amd import rrt, scenes
 
     raw = scenes.config5_field() if star else scenes.field512()
@@ -611,6 +682,8 @@ def run_batch(args, D, star, with_cpu):
     stt = batch.state()
     n, its = stt[0], stt[1]
     st_timed = batch.stats()
+    if args.dump_outputs and D.rank == 0:
+        dump_batch(args.dump_outputs, batch, star)
     dig = batch_digests(batch, star)
     cols = [np.arange(a, b, dtype=np.int64), its.astype(np.int64), n.astype(np.int64), dig]
     t_plan = None
@@ -658,25 +731,27 @@ def run_batch(args, D, star, with_cpu):
         ideal = -(-steps // (args.batch_window or auto_batch_window(b - a)))
         extra["passes"] = {"steps": int(st_timed["batch_steps"]),
                            "host_passes": int(st_timed["batch_passes"]), "ideal_steps": ideal}
-    # profiled pass (same workload, same streams): HIP events around every kernel of every step
     batch.close()
-    batch = fresh()
-    batch.set_profiling(True)
-    batch.extend(steps)
-    sp = batch.stats()
-    evals_p = batch.state()[2] if star else batch.state(with_evals=True)[2]
-    if not star and not args.pmc_run:
-        batch.plan()
-        extra["plan"]["roofline"] = finish_roofline(batch.stats())
-    batch.close()
-    wl = "config5" if star else "config3"
-    # the counter passes were taken on one GPU: the whole 8192-query batch, and config 3's
-    # 1024-query shard (an 8-GPU rank's share)
-    pkey = wl if args.queries == 8192 else f"{wl}_q{args.queries}"
-    pmc = load_profile("batch_pmc.json").get(pkey, {}) if D.world == 1 else {}
-    evals_total = float(evals_p.sum())
-    roof = walk_roofline(sp, pmc.get("steer_walk", {}), wl)
-    nn_roof = lockstep_nn_roofline(sp, evals_total, star, pmc)
+    sp, roof, nn_roof = None, None, None
+    if args.full:
+        # profiled pass (same workload, same streams): HIP events around every kernel of every step
+        batch = fresh()
+        batch.set_profiling(True)
+        batch.extend(steps)
+        sp = batch.stats()
+        evals_p = batch.state()[2] if star else batch.state(with_evals=True)[2]
+        if not star and not args.pmc_run:
+            batch.plan()
+            extra["plan"]["roofline"] = finish_roofline(batch.stats())
+        batch.close()
+        wl = "config5" if star else "config3"
+        # the counter passes were taken on one GPU: the whole 8192-query batch, and config 3's
+        # 1024-query shard (an 8-GPU rank's share)
+        pkey = wl if args.queries == 8192 else f"{wl}_q{args.queries}"
+        pmc = load_profile("batch_pmc.json").get(pkey, {}) if D.world == 1 else {}
+        evals_total = float(evals_p.sum())
+        roof = walk_roofline(sp, pmc.get("steer_walk", {}), wl)
+        nn_roof = lockstep_nn_roofline(sp, evals_total, star, pmc)
     res = {
         "value": round(iters_total / t_max, 1),
         "unit": "iterations/s",
@@ -697,8 +772,9 @@ def run_batch(args, D, star, with_cpu):
         **extra,
     }
     if not star:
-        launches = max(sp["nn_scan_launches"], 1)
         res["schedule"] = "lockstep (four launches per step, two sub-batch streams)"
+    if not star and sp is not None:
+        launches = max(sp["nn_scan_launches"], 1)
         res["step_chain_us"] = {"mq_sample_nn": round(1e3 * sp["nn_scan_ms"] / launches, 2),
                                 "steer_prep": round(1e3 * sp["prep_ms"] / launches, 2),
                                 "steer_walk": round(1e3 * sp["steer_ms"] / launches, 2),
@@ -885,20 +961,21 @@ def run_config1(args, D, with_cpu, polygons=False):
                         "nodes": acc + 1, "stats": {k: st[k] for k in STAT_KEYS}}
         runs[str(K)] = best
     kbest = max(runs, key=lambda k: runs[k]["iterations_per_s"])
-    p = make_planner(raw, args.seed, int(kbest), D.device, capacity=1 << 14)
-    p.set_profiling(True)
-    p.extend(n_iter)
-    p.synchronize()
-    sp = p.stats()
-    p.close()
     name = "config1_polygons" if polygons else "config1"
     geom = ("create_circle polygons + ring bounds, exact Minkowski buffers (Q10p)" if polygons
             else "analytic discs r + w/2 (Q10)")
     res = {"value": runs[kbest]["iterations_per_s"], "unit": "iterations/s", "window": int(kbest),
            "workload": f"{name}: bench6 (benches/all.rs:8-42: 6 obstacles, R 0.8, step 0.1; "
                        f"{geom}), seed {args.seed}, {n_iter} iterations from the root",
-           "per_window": runs,
-           "roofline": dominant_kernel(sp, walk_name=name)}
+           "per_window": runs, "roofline": None}
+    if args.full:  # a profiled run at the best K
+        p = make_planner(raw, args.seed, int(kbest), D.device, capacity=1 << 14)
+        p.set_profiling(True)
+        p.extend(n_iter)
+        p.synchronize()
+        sp = p.stats()
+        p.close()
+        res["roofline"] = dominant_kernel(sp, walk_name=name)
     if with_cpu:
         oracle = oracle_mod()
         sc = oracle.OracleScene.from_raw(raw)
@@ -945,19 +1022,21 @@ def run_plan(args, D, with_cpu, example=False):
                 "check_finish_nodes": len(nodes),
                 "check_finish_ms": round(1e3 * dcf, 3),
                 "check_finish_per_s": round(len(nodes) / dcf, 1)}
-    p = make_planner(raw, args.seed, 512, D.device, capacity=1 << 14)
-    p.set_profiling(True)
-    p.plan(n_iter)
-    sp = p.stats()
-    p.close()
+    sp = None
+    if args.full:  # a profiled run for the check_finish roofline
+        p = make_planner(raw, args.seed, 512, D.device, capacity=1 << 14)
+        p.set_profiling(True)
+        p.plan(n_iter)
+        sp = p.stats()
+        p.close()
     scene = ("examples/rrt: transit.debug.json (20-vertex bounds ring, 3 polygon obstacles), "
              "Robot(1.8, 3.0, 0.8)" if example else
              "bench6_open (bench6 scene, start (-3, -3, 45 deg))")
     res = {"value": best["plan_calls_per_s"], "unit": "plan_one calls/s (with check_finish)",
            "workload": f"{'example_rrt' if example else 'plan'}: {scene}, seed {args.seed}, "
                        f"RRT::plan with {n_iter} iterations", **best,
-           "roofline": finish_roofline(sp),
-           "extend_window_chain_us": window_chain(sp)}
+           "roofline": finish_roofline(sp) if sp else None,
+           "extend_window_chain_us": window_chain(sp) if sp else None}
     if with_cpu:
         oracle = oracle_mod()
         sc = oracle.OracleScene.from_raw(raw)
@@ -1114,7 +1193,8 @@ def compact_line(line, detail_path=None, with_subs=True):
     prov = line.get("provenance") or {}
     head["lib_sha256_16"] = prov.get("lib_sha256_16")
     if detail_path:
-        head["detail"] = os.path.relpath(detail_path, ROOT)
+        rel = os.path.relpath(detail_path, ROOT)
+        head["detail"] = detail_path if rel.startswith(os.pardir) else rel
     s = line_json(head)
     # over the cap (long error texts, many sub-results): shed the least important fields first
     for drop in (("sub", "workload"), ("cpu_baseline", "sample"), ("sub", "kernel"),
@@ -1136,9 +1216,20 @@ def compact_line(line, detail_path=None, with_subs=True):
 
 
 def write_detail(path, s):
-    os.makedirs(os.path.dirname(path), exist_ok=True)
-    with open(path, "w") as f:
-        f.write(s + "\n")
+    """Writes the full record to `path`, or, where that cannot be written (a read-only checkout),
+    under the temporary directory.  Returns where it went, or None: the record is a by-product and
+    never costs the run its result line."""
+    fallback = os.path.join(tempfile.gettempdir(), f"bench_detail_{os.getuid()}.json")
+    for p in (path, fallback):
+        try:
+            os.makedirs(os.path.dirname(p), exist_ok=True)
+            with open(p, "w") as f:
+                f.write(s + "\n")
+            return p
+        except OSError as e:
+            print(f"bench.py: the detail record could not be written to {p}: {e}",
+                  file=sys.stderr)
+    return None
 
 
 def tree_line(args, D, workload, raw, res):
@@ -1213,6 +1304,7 @@ def sub(D, fn, *a):
 def tree_sub(args, D, raw, workload, cpu):
     ta = argparse.Namespace(**vars(args))
     ta.no_size_sweep = True
+    ta.dump_outputs = None  # --dump-outputs holds the headline workload's arrays
     res = {k: v for k, v in run_tree(ta, D, raw, workload, cpu).items()
            if k not in ("sizes", "t_max")}
     res.setdefault("unit", "iterations/s")
@@ -1225,7 +1317,7 @@ def main():
         return spawn_ranks(args.gpus)
     D = Dist(args)
     prov = provenance(args)
-    cpu = D.rank == 0 and D.world == 1 and not args.no_cpu_baseline
+    cpu = args.full and D.rank == 0 and D.world == 1 and not args.no_cpu_baseline
     from pathplanning_amd import scenes
 
     wl = args.workload
@@ -1234,9 +1326,10 @@ def main():
         raw = {"config4": scenes.field512_grid, "polygons": scenes.field512_polygons}.get(
             tw, scenes.field512)()
         line = tree_line(args, D, tw, raw, run_tree(args, D, raw, tw, cpu))
-        if wl == "default" and not args.no_sub:
+        if wl == "default" and args.full and not args.no_sub:
             sa = argparse.Namespace(**vars(args))
             sa.steps = None  # the batches run their whole max_iter
+            sa.dump_outputs = None
             line["config3"] = sub(D, run_batch, sa, D, False, cpu)
             line["config5"] = sub(D, run_batch, sa, D, True, cpu)
             if D.world == 1:
@@ -1269,8 +1362,7 @@ def main():
                                   "scaling": "strong",
                                   "records_digest": line["config3"].get("records_digest")}
     if D.rank == 0:
-        detail = os.path.abspath(args.detail)
-        write_detail(detail, line_json(line))
+        detail = write_detail(os.path.abspath(args.detail), line_json(line))
         print(compact_line(line, detail, wl == "default"), flush=True)
     D.close()
     return 0

@@ -6,9 +6,9 @@ OUT="gpurun_out/${TAG:-c5ab}"
 mkdir -p "$OUT"
 for v in ${VARIANTS:-base}; do
   if [ "$v" = base ]; then
-    timeout -k 10 300 python -u bench.py --workload config5 --no-cpu-baseline > "$OUT/c5_$v.json" 2> "$OUT/c5_$v.err" || { tail -20 "$OUT/c5_$v.err"; exit 1; }
+    timeout -k 10 300 python -u bench.py --full --workload config5 --no-cpu-baseline > "$OUT/c5_$v.json" 2> "$OUT/c5_$v.err" || { tail -20 "$OUT/c5_$v.err"; exit 1; }
   else
-    PP_AMD_LIB="$PWD/rs-pathplanning_amd/lib/$v/libpathplanning_amd.so" timeout -k 10 300 python -u bench.py --workload config5 --no-cpu-baseline --allow-variant-lib > "$OUT/c5_$v.json" 2> "$OUT/c5_$v.err" || { tail -20 "$OUT/c5_$v.err"; exit 1; }
+    PP_AMD_LIB="$PWD/rs-pathplanning_amd/lib/$v/libpathplanning_amd.so" timeout -k 10 300 python -u bench.py --full --workload config5 --no-cpu-baseline --allow-variant-lib > "$OUT/c5_$v.json" 2> "$OUT/c5_$v.err" || { tail -20 "$OUT/c5_$v.err"; exit 1; }
   fi
   echo "done c5 $v"
 done

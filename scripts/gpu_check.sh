@@ -1,6 +1,7 @@
 #!/bin/bash
 # One GPU check: the -m gpu tests (or the files given in TESTS), then a bench line (BENCH_ARGS),
 # each under its own time limit; everything under gpurun_out/$TAG.
+# (BENCH_ARGS / BENCH2_ARGS: with --full for the profiled passes, CPU baselines and sub-results)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="gpurun_out/${TAG:-check}"

@@ -12,10 +12,10 @@ SQA="GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INS
 SQB="SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS"
 args() {
   case $1 in
-    config2|config4) echo "--workload $1 --steps 20 --warmup 3 --no-cpu-baseline --no-size-sweep" ;;
-    config3) echo "--workload $1 --warmup 3 --no-cpu-baseline --pmc-run" ;;
-    config3s) echo "--workload config3 --queries 1024 --warmup 3 --no-cpu-baseline --pmc-run" ;;
-    config5) echo "--workload $1 --warmup 3 --no-cpu-baseline --max-iter 600" ;;  # (PMC of 2000 steps crashed the profiler)
+    config2|config4) echo "--full --workload $1 --steps 20 --warmup 3 --no-cpu-baseline --no-size-sweep" ;;
+    config3) echo "--full --workload $1 --warmup 3 --no-cpu-baseline --pmc-run" ;;
+    config3s) echo "--full --workload config3 --queries 1024 --warmup 3 --no-cpu-baseline --pmc-run" ;;
+    config5) echo "--full --workload $1 --warmup 3 --no-cpu-baseline --max-iter 600" ;;  # (PMC of 2000 steps crashed the profiler)
   esac
 }
 for wl in ${WLS:-config2 config4 config3 config5}; do

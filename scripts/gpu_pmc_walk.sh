@@ -1,6 +1,7 @@
 #!/bin/bash
 # Stall-side counter passes of one kernel under a bench workload (each pass its own rocprofv3 run):
 # instruction-cache traffic, wait / issue / level counters.  KERNEL, ARGS, TAG.
+# (ARGS: bench arguments, with --full when the profiled pass's dispatches are the ones wanted)
 set -o pipefail
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$R/gpurun_out/${TAG:-pmcw}"

@@ -13,7 +13,7 @@ for q in ${QUERIES:-8192 1024}; do
   for sch in ${SCHEDULES:-persistent lockstep}; do
     for v in ${VARIANTS:-base}; do
       if [ "$v" = base ]; then LIBENV=""; ALLOW=""; else LIBENV="PP_AMD_LIB=$PWD/rs-pathplanning_amd/lib/$v/libpathplanning_amd.so"; ALLOW="--allow-variant-lib"; fi
-      env $LIBENV timeout -k 10 300 python -u bench.py --workload config3 --queries $q --schedule $sch --no-cpu-baseline $ALLOW $EXTRA > "$OUT/c3_${q}_${sch}_${v}.json" 2> "$OUT/c3_${q}_${sch}_${v}.err" || { tail -20 "$OUT/c3_${q}_${sch}_${v}.err"; exit 1; }
+      env $LIBENV timeout -k 10 300 python -u bench.py --full --workload config3 --queries $q --schedule $sch --no-cpu-baseline $ALLOW $EXTRA > "$OUT/c3_${q}_${sch}_${v}.json" 2> "$OUT/c3_${q}_${sch}_${v}.err" || { tail -20 "$OUT/c3_${q}_${sch}_${v}.err"; exit 1; }
       echo "done $q $sch $v"
     done
   done

@@ -5,6 +5,8 @@
 # (<name>_<rep>.cmd), so a cited record names the exact command that produced it.
 #   RUNS="name|var|bench args;..."   var: "base" = the in-tree library, else
 #                                    rs-pathplanning_amd/lib/<var>/libpathplanning_amd.so
+#                                    bench args: with --full for the profiled passes, CPU
+#                                    baselines and sub-results
 #   REPS="1 2"                       repetitions (alternated: every run of rep 1, then rep 2, ...)
 set -o pipefail
 R="${GRAFT_REPO_ROOT:-/root/repo}"

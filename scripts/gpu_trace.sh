@@ -2,12 +2,13 @@
 # Kernel-trace summaries (rocprofv3 --kernel-trace --stats, no counters) of bench.py workloads, one
 # run each: gpurun_out/$TAG/<name>/..._kernel_stats.csv plus the bench line of the traced run.
 # RUNS: "name|bench args;name|bench args;..."
+# (bench args: with --full for the profiled passes, CPU baselines and sub-results)
 set -o pipefail
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$R/gpurun_out/${TAG:-trace}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-IFS=';' read -ra JOBS <<< "${RUNS:-config3|--workload config3 --no-cpu-baseline}"
+IFS=';' read -ra JOBS <<< "${RUNS:-config3|--full --workload config3 --no-cpu-baseline}"
 for j in "${JOBS[@]}"; do
   name=${j%%|*}
   args=${j#*|}

@@ -2,6 +2,7 @@
 # Kernel traces of bench workloads against the in-tree library or a variant (VAR=<name>:
 # rs-pathplanning_amd/lib/<name>/), one rocprofv3 --kernel-trace --stats run each.
 # RUNS: "name|var|bench args;..." (var "base" = in-tree)
+# (bench args: with --full for the profiled passes, CPU baselines and sub-results)
 set -o pipefail
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$R/gpurun_out/${TAG:-tracevar}"

@@ -72,6 +72,30 @@ def test_default_line_fits_the_driver_tail():
     assert back["detail"] == "gpurun_out/bench_detail.json"
 
 
+def test_detail_record_falls_back_when_its_place_cannot_be_written(tmp_path, monkeypatch):
+    """A checkout the run may not write to still gets its result line: the detail record goes to
+    the temporary directory instead, and the line names where it went."""
+    import tempfile
+
+    bench = _bench()
+    tmp = tmp_path / "tmp"
+    tmp.mkdir()
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp))
+    ok = tmp_path / "out" / "detail.json"  # created on demand
+    assert bench.write_detail(str(ok), "{}") == str(ok) and ok.read_text() == "{}\n"
+    blocker = tmp_path / "file"
+    blocker.write_text("")
+    went = bench.write_detail(str(blocker / "sub" / "detail.json"), '{"a": 1}')
+    assert os.path.dirname(went) == str(tmp)
+    with open(went) as f:
+        assert json.load(f) == {"a": 1}
+    back = json.loads(bench.compact_line({"metric": bench.METRIC, "value": 1.0}, went))
+    assert back["detail"] == went  # outside the tree: the whole path
+    monkeypatch.setattr(tempfile, "tempdir", str(blocker / "nowhere"))
+    assert bench.write_detail(str(blocker / "sub" / "detail.json"), "{}") is None
+    assert "detail" not in json.loads(bench.compact_line({"metric": bench.METRIC, "value": 1.0}))
+
+
 def test_compact_line_sheds_fields_over_the_cap():
     """A line swollen by long error texts still fits: the least important fields go first."""
     bench = _bench()
