@@ -1,0 +1,448 @@
+// pp_ctx.h — what the host API's source files share: the error helpers, the device / pinned
+// buffers, the context (pp_ctx) with one member per subsystem, and the few cross-file helpers.
+//   pp_context.cpp  context, errors, statistics, profiling, the Dubins entry points
+//   pp_space.cpp    the scene
+//   pp_rrt.cpp      the one-tree planner and its window buffers
+//   pp_finish.cpp   check_finish / optimize / finalize, pp_rrt_plan, pp_batch_plan
+//   pp_batch.cpp    the forest of per-query trees, pp_batch_*, pp_star_*
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/pathplanning_amd.h"
+#include "pp_device.h"
+#include "pp_kernels.h"
+#include "pp_scene.h"
+
+namespace ppamd {
+
+int set_err(int code, const std::string& msg);  // (the thread's pp_last_error)
+
+#define PP_HIP(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return set_err(PP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+// a grow-only buffer of n elements in device memory, or (kPinned) in pinned host memory
+template <typename T, bool kPinned = false>
+struct DBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    hipError_t reserve(size_t count) {
+        if (count <= n) return hipSuccess;
+        release();
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        hipError_t e = kPinned ? hipHostMalloc(reinterpret_cast<void**>(&p), bytes, hipHostMallocDefault)
+                               : hipMalloc(reinterpret_cast<void**>(&p), bytes);
+        if (e == hipSuccess) n = count;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        n = 0;
+    }
+    ~DBuf() { release(); }
+};
+template <typename T>
+using HBuf = DBuf<T, true>;  // pinned host staging
+
+constexpr int kMaxBatch = 64;  // windows enqueued between two host synchronisations
+constexpr int kInsideCells = 2048;  // the inside bitmap's cells per axis (point_blocked)
+constexpr int kScreenPad = 64;  // f32 screen copies: the LDS-DMA reads whole float4s (<= 3 floats past)
+constexpr int kMaxSub = 4;  // sub-batches of a query batch, each on its own stream
+
+// ---- scene (Space)
+struct Scene {
+    bool valid = false;  // pp_space_new / pp_space_new_polygons succeeded
+    double minx = 0, maxx = 0, miny = 0, maxy = 0;
+    double width = 0, height = 0, max_steer = 0;
+    int m = 0;
+    DBuf<double> d_cx, d_cy, d_r2, d_rcull;
+    DBuf<int> d_goff, d_gitems;
+    DBuf<uint4> d_img, d_gimg;  // LDS images (discs / occupancy bits), contiguous
+    double gx0 = 0, gy0 = 0, ginv = 1;
+    int gnx = 1, gny = 1;
+    int lds_bytes = 0, lds_goff = 0, lds_items = 0, lds_cx = 0, lds_cy = 0, lds_r2 = 0, lds_d4 = 0;
+    DBuf<float4> d_d4;
+    // occupancy grid (config 4)
+    bool has_grid = false;
+    DBuf<uint32_t> d_bits;
+    int bw = 0, bh = 0, bwords = 0, lds_bits_bytes = 0;
+    double bx0 = 0, by0 = 0, binv = 1;
+    // polygon mode (pp_space_new_polygons, Q10p): obstacle edges, bounds ring; host copies for
+    // the point checks (root / query starts)
+    // disc scenes: the inside bitmap (scene::inside_bitmap), the point_blocked pre-test
+    DBuf<uint32_t> d_ibits;
+    int ibn = 0;
+    double ibx0 = 0.0, iby0 = 0.0, ibinv = 1.0;
+    int ne = 0, nbv = 0;
+    double h2 = 0.0;
+    float cull_slack = 1.0e-3f;
+    DBuf<double> d_ex0, d_ey0, d_ex1, d_ey1, d_bvx, d_bvy;
+    DBuf<int> d_epoly;
+    std::vector<double> h_ex0, h_ey0, h_ex1, h_ey1, h_bvx, h_bvy;
+    std::vector<int> h_epoly;
+
+    bool polygons() const { return ne > 0 || nbv > 0; }
+    // the kernels' view, with the caller's step size and (one-tree planner) blocked root
+    SceneDev dev(double step, bool root_blocked) const {
+        SceneDev s;
+        s.minx = minx;
+        s.maxx = maxx;
+        s.miny = miny;
+        s.maxy = maxy;
+        s.turn_radius = max_steer;
+        s.step_size = step;
+        s.m = m;
+        s.cx = d_cx.p;
+        s.cy = d_cy.p;
+        s.r2 = d_r2.p;
+        s.rcull = d_rcull.p;
+        s.gx0 = gx0;
+        s.gy0 = gy0;
+        s.ginv = ginv;
+        s.gcell = 1.0 / ginv;
+        s.gnx = gnx;
+        s.gny = gny;
+        s.goff = d_goff.p;
+        s.gitems = d_gitems.p;
+        s.lds_bytes = lds_bytes;
+        s.lds_goff = lds_goff;
+        s.lds_items = lds_items;
+        s.lds_cx = lds_cx;
+        s.lds_cy = lds_cy;
+        s.lds_r2 = lds_r2;
+        s.d4 = d_d4.p;
+        s.lds_d4 = lds_d4;
+        s.bits = has_grid ? d_bits.p : nullptr;
+        s.bw = bw;
+        s.bh = bh;
+        s.bwords = bwords;
+        s.bx0 = bx0;
+        s.by0 = by0;
+        s.binv = binv;
+        s.img = d_img.p;
+        if (has_grid) {
+            s.lds_bytes = lds_bits_bytes;
+            s.img = d_gimg.p;
+        }
+        s.ne = ne;
+        s.ex0 = d_ex0.p;
+        s.ey0 = d_ey0.p;
+        s.ex1 = d_ex1.p;
+        s.ey1 = d_ey1.p;
+        s.epoly = d_epoly.p;
+        s.h2 = h2;
+        s.nbv = nbv;
+        s.bvx = d_bvx.p;
+        s.bvy = d_bvy.p;
+        s.cull_slack = cull_slack;
+        s.root_blocked = root_blocked ? 1 : 0;
+        s.ibits = ibn > 0 ? d_ibits.p : nullptr;
+        s.ibn = ibn;
+        s.ibwords = ibn / 32;
+        s.ibx0 = ibx0;
+        s.iby0 = iby0;
+        s.ibinv = ibinv;
+        return s;
+    }
+    // Space::verify of the one-point line [(x, y)] on the host, polygon mode (Q10p; the same
+    // arithmetic as the kernels and the oracle): bounds, edge buffers, inside an obstacle
+    bool point_ok(double x, double y) const {
+        SceneDev s = dev(0.0, false);  // (bounds, nbv, h2) with the ring's host copy
+        s.bvx = h_bvx.data();
+        s.bvy = h_bvy.data();
+        if (!point_in_bounds(s, x, y)) return false;
+        for (int k = 0; k < ne; ++k)
+            if (seg_hits_edge(x, y, x, y, h_ex0[k], h_ey0[k], h_ex1[k], h_ey1[k], h2)) return false;
+        return !in_obstacle(ne, h_ex0.data(), h_ey0.data(), h_ex1.data(), h_ey1.data(),
+                            h_epoly.data(), x, y);
+    }
+};
+
+// ---- planner (RRT): the one tree and its window buffers
+struct Planner {
+    bool valid = false;  // pp_rrt_new succeeded for the current scene
+    double start[3] = {0, 0, 0}, goal[3] = {0, 0, 0};
+    int64_t max_iter = 0;
+    double step = 0.1;
+    uint64_t seed = 0;
+    int64_t it = 0;   // mirror of DevState.it (exact after every synchronisation)
+    int64_t seq = 0;  // windows enqueued so far (their sequence numbers)
+    int64_t n = 0;    // mirror of DevState.n
+    int64_t cap = 0;  // tree capacity
+    double eps_coord = 0.0;
+    bool root_blocked = false;  // polygon mode: the root fails verify (nothing is ever inserted)
+    DBuf<float> x32, y32;
+    DBuf<double> X, Y, YAW;
+    DBuf<int> PAR;
+    DBuf<DevState> d_state, d_api_state;
+    HBuf<DevState> h_state;
+    // pp_rrt_extend_samples: the caller's samples and the per-iteration record (one chunk)
+    DBuf<double> hs_x, hs_y, hs_yaw;
+    DBuf<int> hs_par;
+    DBuf<uint8_t> hs_ok;
+
+    // ---- window buffers (sized for Kcap)
+    int K = 4096;
+    int Kcap = 0;
+    DBuf<double> wsx, wsy, nn_d2, snap_yaw, snap_pose;
+    DBuf<float> pbest, psecond, wsx32, wsy32;
+    DBuf<int> perm, cofs, ipos;
+    DBuf<float2> sxy;
+    DBuf<double> sqb, ssx, ssy;
+    DBuf<float2> ob;
+    DBuf<int> pidx, nn_idx, cand_cnt, snap_status;
+    DBuf<CandEntry> cand;
+    DBuf<PrepRec> rec;   // per-task steer records
+    DBuf<int> r_order, r_rep, pend, fin_par;
+    DBuf<unsigned char> blk;   // [2 Kcap] window samples in an obstacle (point_blocked)
+    DBuf<SceneDev> d_scene;    // the scene in device memory (samples_role, the literal paths)
+    DBuf<double> r_repyaw;
+    DBuf<double> lit_scratch;  // resolve: one literal buffer per wave
+    // verify_node API
+    DBuf<SteerTask> tasks;
+    DBuf<int> task_status;
+    DBuf<double> task_yaw;
+    HBuf<SteerTask> h_tasks;
+
+    TreeDev tree_dev() const {
+        TreeDev t;
+        t.x32 = x32.p;
+        t.y32 = y32.p;
+        t.x = X.p;
+        t.y = Y.p;
+        t.yaw = YAW.p;
+        t.parent = PAR.p;
+        return t;
+    }
+    WindowArgs window_args(const SceneDev& sc, long long* wg_points, DevState* st) const {
+        WindowArgs a;
+        a.K = Kcap;
+        a.Kcap = Kcap;
+        a.seed = seed;
+        a.eps_coord = eps_coord;
+        a.st = st;
+        a.sc = sc;
+        a.tr = tree_dev();
+        a.wsx = wsx.p;
+        a.wsy = wsy.p;
+        a.wsx32 = wsx32.p;
+        a.wsy32 = wsy32.p;
+        a.perm = perm.p;
+        a.cofs = cofs.p;
+        a.sxy = sxy.p;
+        a.sq = sqb.p;
+        a.ssx = ssx.p;
+        a.ssy = ssy.p;
+        a.ob = ob.p;
+        a.ipos = ipos.p;
+        a.pbest = pbest.p;
+        a.psecond = psecond.p;
+        a.pidx = pidx.p;
+        a.nn_idx = nn_idx.p;
+        a.nn_d2 = nn_d2.p;
+        a.cand_cnt = cand_cnt.p;
+        a.cand = cand.p;
+        a.snap_status = snap_status.p;
+        a.snap_yaw = snap_yaw.p;
+        a.snap_pose = snap_pose.p;
+        a.rec = rec.p;
+        a.pend = pend.p;
+        a.fin_par = fin_par.p;
+        a.rs.order = r_order.p;
+        a.rs.rep = r_rep.p;
+        a.rs.repyaw = r_repyaw.p;
+        a.lit_scratch = lit_scratch.p;
+        a.wg_points = wg_points;
+        a.scp = d_scene.p;
+        a.blk = d_scene.p ? blk.p : nullptr;
+        return a;
+    }
+};
+
+// ---- check_finish buffers (cf_run, cf_run_rounds)
+struct Finish {
+    DBuf<SceneDev> scene;   // check_finish_kernel's scene (its step may be a batch's)
+    SceneDev scene_host{};  // what `scene` holds (the source of its last upload)
+    bool scene_ok = false;
+    DBuf<int> nodes, ok, npts, chain, etab, err, path, items;
+    DBuf<int> lpath, spill;  // cf_line_kernel's ancestor paths; tier 1's spill list
+    DBuf<int> memo;  // check_finish_kernel's optimize memo (CfBatch::ftab / gtab), per launch
+    DBuf<double> len, pts;
+};
+
+// ---- a forest of per-query SoA trees: the host side of MqDev's shared part, under both the
+// extend batch (config 3) and the RRT* batch (config 5).  Tree q lives in rows [q * cap, q * cap +
+// n[q]); the forest runs as nsub sub-batches of consecutive queries, each on its own stream.
+struct Forest {
+    int Q = 0, cap = 0;
+    int64_t max_iter = 0;
+    double step = 0.1;
+    int nsub = 1;  // fixed by init(): the sub-batch DevStates are written for this split
+    bool any_blocked = false;
+    DBuf<double> x, y, yaw;  // [Q * cap]
+    DBuf<int> parent;
+    DBuf<int> n;             // [Q] and below
+    DBuf<int64_t> it, evals;
+    DBuf<int64_t> target;    // iteration targets of the running extend call
+    DBuf<uint64_t> seed;
+    DBuf<uint8_t> blocked;   // polygon mode: the root fails verify
+    DBuf<double> d_starts;   // [3Q] the roots as uploaded (the init kernels read them)
+
+    // reserve q trees of max_iter + 1 rows, upload the roots (RRT::new per query, rrt.rs:344-346:
+    // row 0 of each tree) and seeds, and test the roots (polygon mode); enqueued on c->stream
+    int init(pp_ctx* c, int q, int64_t max_iter_, double step_, const double* starts,
+             const uint64_t* seeds, int nsub_);
+    MqDev dev() const;  // the kernels' view of the shared fields (the whole forest)
+    int q_begin(int s) const { return (int)((int64_t)Q * s / nsub); }  // sub-batch s: [q_begin(s), q_begin(s + 1))
+    // d restricted to the queries [q0, q1): the one place that offsets the shared pointers
+    MqDev sub(MqDev d, int q0, int q1) const;
+    const uint8_t* blocked_dev() const { return any_blocked ? blocked.p : nullptr; }
+    TreeDev tree_dev() const;  // the SoA rows (query q: offset q * cap)
+    // The copy-outs below take one more array of the same shape (`extra`: RRT*'s rewires / cost)
+    // and synchronise once.  Sums over the queries of it, n and extra:
+    int totals(pp_ctx* c, int64_t* it_sum, int64_t* n_sum, const int64_t* extra = nullptr,
+               int64_t* extra_sum = nullptr) const;
+    // the per-query counters (a null output is skipped)
+    int copy_state(pp_ctx* c, int32_t* n_nodes, int64_t* iterations, int64_t* node_evals,
+                   const int64_t* extra = nullptr, int64_t* extra_out = nullptr) const;
+    // one tree's rows (*n_out: its nodes, also when ocap is too small)
+    int export_tree(pp_ctx* c, int query, double* ox, double* oy, double* oyaw, int32_t* oparent,
+                    int64_t ocap, int64_t* n_out, const double* extra = nullptr,
+                    double* extra_out = nullptr) const;
+};
+
+// ---- multi-query batch (config 3): the forest plus the speculative-window arrays, and
+// pp_batch_plan's buffers
+struct Batch {
+    bool valid = false;  // false on entry to pp_batch_new, true only on its success
+    Forest f;
+    DBuf<double> yawbuf;
+    DBuf<int> status, err, alist, lstat;
+    DBuf<int64_t> itprev;      // the lockstep NN's verdict cache (MqDev::it_prev)
+    int K = 1;                 // speculative window per query of the current batch
+    int K_user = 0;            // pp_batch_set_window (0: automatic)
+    DBuf<double> nnd2;         // [Q * kMqMaxK]
+    DBuf<SteerTask> tasks, ctask;
+    DBuf<PrepRec> rec;
+    DBuf<DevState> state;      // [1 + kMaxSub]: the whole batch, then one per sub-batch (mq_sub_args)
+    DBuf<SceneDev> scene;      // the scene in device memory (point_blocked)
+    std::vector<double> goal;  // 3 per query (RRT::new's goal; pp_batch_plan)
+    DBuf<double> goal_d;       // [3Q] the goals on the device (pp_batch_plan)
+    DBuf<int> mp_off, mp_qidx, mp_nodes, mp_ok, mp_npts, mp_best, mp_bpts, mp_nfin;
+    DBuf<double> mp_len, mp_blen;
+    // pp_batch_plan's check_finish in steer rounds (CfbArgs)
+    DBuf<int> cfb_nodei;   // [4 (nitems + Q)]: depth, open, tfirst, tcnt
+    DBuf<int> cfb_rows;    // [rows]: gclaim
+    DBuf<unsigned char> cfb_rows8;  // [2 rows]: tnone, tnone_up
+    DBuf<int> cfb_gotab, cfb_plist, cfb_tnode, cfb_status, cfb_misc, cfb_lit, cfb_dhist;
+    DBuf<SteerTask> cfb_tasks;
+    DBuf<StarTaskExt> cfb_ext;
+    DBuf<PrepRec> cfb_rec;
+    DBuf<unsigned char> cfb_none;
+    DBuf<double> cfb_yaw;
+    DBuf<DevState> cfb_state;
+    DBuf<long long> cfb_pts;  // profiling: the rounds' walk point tallies
+    bool cf_rounds = true;  // pp_batch_plan in steer rounds (pp_batch_set_finish_schedule)
+    int cfb_span0 = kCfbSpan, cfb_span = kCfbSpan;  // phase A candidates per node: first / later rounds
+};
+
+// ---- RRT* query batch (BASELINE config 5, build-defined: DESIGN.md §3.7): the forest plus costs,
+// the kNN slots and the three rounds' task arrays
+struct StarBatch {
+    bool valid = false;  // false on entry to pp_star_new, true only on its success
+    Forest f;
+    int kfix = 0;
+    double eta = 0.0;
+    DBuf<double> cost, elen, px, py, cb;
+    DBuf<int> mark, stamp, ksched, pn, near, nnear, bslot, cslot, err;
+    DBuf<uint64_t> cmask, bmask;
+    DBuf<int64_t> rew;
+    DBuf<DevState> state;  // [3 * (1 + kMaxSub)]: rounds A, B, C of the batch, then per sub-batch
+    DBuf<SteerTask> tA, tB, tC;
+    DBuf<StarTaskExt> eB, eC;
+    DBuf<int> sA, sB, sC;
+    DBuf<double> yA, yB, yC, cA, cB, cC;
+    DBuf<PrepRec> rec;
+};
+
+// ---- profiling
+struct Profiling {
+    bool on = false;
+    std::vector<hipEvent_t> ev;  // 4 per window or batch step, 8 per RRT* step
+    double nn_scan_ms = 0.0, steer_ms = 0.0, finish_ms = 0.0, finalize_ms = 0.0, prep_ms = 0.0,
+           insert_ms = 0.0;
+    int64_t nn_scan_launches = 0, steer_launches = 0, finish_launches = 0;
+    int64_t batch_steps = 0, batch_passes = 0;
+    int64_t cfb_nodes = 0, cfb_edges = 0, cfb_points = 0, cfb_arc = 0;  // the batch plan's steer rounds
+    DBuf<long long> cf_tally;  // check_finish (profiling): nodes, edges, points, arc points
+    DBuf<long long> wg_pts;  // walked polyline points per walk workgroup (profiling on)
+    long long* points() const { return on ? wg_pts.p : nullptr; }
+    // every counter of pp_stats that lives on the host or in the profiling tallies (not DevState)
+    int reset_host_stats(hipStream_t stream) {
+        nn_scan_ms = steer_ms = finish_ms = finalize_ms = prep_ms = insert_ms = 0.0;
+        nn_scan_launches = steer_launches = finish_launches = 0;
+        batch_steps = batch_passes = 0;
+        cfb_nodes = cfb_edges = cfb_points = cfb_arc = 0;
+        if (wg_pts.p && hipMemsetAsync(wg_pts.p, 0, wg_pts.n * sizeof(long long), stream) != hipSuccess)
+            return PP_ERR_HIP;
+        if (cf_tally.p && hipMemsetAsync(cf_tally.p, 0, cf_tally.n * sizeof(long long), stream) != hipSuccess)
+            return PP_ERR_HIP;
+        return hipStreamSynchronize(stream) == hipSuccess ? PP_OK : PP_ERR_HIP;
+    }
+    ~Profiling() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+}  // namespace ppamd
+
+struct pp_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t sub_stream[ppamd::kMaxSub] = {};  // sub-batch streams 1.. (0 is `stream`), created on first use
+    hipEvent_t fork_ev = nullptr;
+    ppamd::DBuf<double> api_lit_scratch;  // literal buffers of the API paths (kLiteralWaves slots)
+    ppamd::DBuf<int> lit_locks;  // literal scratch slot locks (api_lit_scratch), zeroed once
+
+    ppamd::Scene scene;
+    ppamd::Planner rrt;
+    ppamd::Finish cf;
+    ppamd::Batch batch;
+    ppamd::StarBatch star;
+    ppamd::Profiling prof;
+
+    // the scene as the one-tree planner's kernels see it (its step, its blocked root)
+    ppamd::SceneDev scene_dev() const { return scene.dev(rrt.step, rrt.root_blocked); }
+
+    ~pp_ctx() {
+        if (fork_ev) (void)hipEventDestroy(fork_ev);
+        for (auto& ss : sub_stream)
+            if (ss) (void)hipStreamDestroy(ss);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace ppamd {
+
+int check_ctx(pp_ctx* c, bool need_scene, bool need_rrt);
+int ensure_events(pp_ctx* c, size_t count);
+// reserve the API literal scratch pool and (once, zeroed on `st`) its slot locks
+int ensure_literal_pool(pp_ctx* c, hipStream_t st);
+
+}  // namespace ppamd

@@ -181,6 +181,7 @@ PATCHES_K = [
 CAPI_TAIL = r"""
 // ---- diagnostic dump (scripts/diag_walk_stamps.py) ----
 extern "C" void ppdiag_setup(void* buf, unsigned cap);
+extern "C" int pp_rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted);
 static void* g_diag_buf = nullptr;
 static void diag_begin() {
     if (!getenv("PP_DIAG_OUT")) return;
@@ -216,11 +217,16 @@ extern "C" int pp_rrt_extend(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted) {
 }
 """
 
+# the wrapped entry points become *_impl where they are defined; CAPI_TAIL (appended to TAIL_FILE)
+# defines the public names around them
+TAIL_FILE = "pp_batch.cpp"
 PATCHES_C = [
-    ("int pp_batch_extend(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t* n_accepted) {",
-     "static int pp_batch_extend_impl(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t* n_accepted) {"),
-    ("int pp_rrt_extend(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted) {",
-     "static int pp_rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted) {"),
+    ("pp_batch.cpp",
+     "int pp_batch_extend(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t* n_accepted) {",
+     "int pp_batch_extend_impl(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t* n_accepted) {"),
+    ("pp_rrt.cpp",
+     "int pp_rrt_extend(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted) {",
+     "int pp_rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted) {"),
 ]
 
 
@@ -234,13 +240,14 @@ def build():
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(BUILD, "include"))
     for f in ge.SOURCES + ge.HEADERS:
         shutil.copy(os.path.join(SRC, f), csrc)
-    for name, patches, tail in (("pp_kernels.hip", PATCHES_K, ""), ("pp_capi.cpp", PATCHES_C, CAPI_TAIL)):
+    patches = [("pp_kernels.hip", a, b) for a, b in PATCHES_K] + PATCHES_C
+    for name in sorted({p[0] for p in patches}):
         p = os.path.join(csrc, name)
         s = open(p).read()
-        for a, b in patches:
+        for a, b in [(a, b) for f, a, b in patches if f == name]:
             assert s.count(a) == 1, (name, a[:60])
             s = s.replace(a, b)
-        open(p, "w").write(s + tail)
+        open(p, "w").write(s + (CAPI_TAIL if name == TAIL_FILE else ""))
     os.makedirs(os.path.dirname(OUTLIB), exist_ok=True)
     cmd = ["/opt/rocm/bin/hipcc", *ge.HIPCC_FLAGS, "-o", OUTLIB] + [os.path.join(csrc, f) for f in ge.SOURCES]
     subprocess.run(cmd, check=True)

@@ -158,6 +158,33 @@ def test_star_sub_batch_streams(pkg, oracle_mod, ctx):
     assert int(n.sum()) - 300 == acc and int(rw.sum()) == rws
 
 
+def test_star_blocked_roots_across_sub_batches(pkg, oracle_mod, ctx):
+    """polygon mode, 300 queries as sub-batches of consecutive queries: blocked roots (a start
+    inside an obstacle polygon, 1 from its edges, robot half width 0.5) on both sides of the
+    boundaries of a split in halves (150) and in thirds (100, 200) and at both ends never insert
+    or rewire; the free queries next to them equal their own oracle runs"""
+    from pathplanning_amd import scenes
+
+    raw = scenes.bench6_polygons_open()
+    inside = (10.0, 5.0, 0.3)  # in the polygon of the disc (9, 5) r 2, outside that of (7, 5) r 2
+    blocked = (0, 99, 100, 149, 150, 199, 200, 299)
+    starts = np.array([raw["start"]] * 300, dtype=np.float64)
+    starts[list(blocked)] = inside
+    seeds = np.arange(2000, 2300, dtype=np.uint64)
+    for q in blocked:  # the oracle never inserts from the blocked start
+        exp, erw = _oracle(oracle_mod, raw, inside, int(seeds[q]), 40, 0, 0.0)
+        assert len(exp[0]) == 1 and erw == 0
+    b = _batch(pkg, raw, starts, seeds, 40, 0, 0.0, ctx=ctx)
+    b.extend(40)
+    n, it, _, rw = b.state()
+    assert (it == 40).all()
+    assert (n[list(blocked)] == 1).all() and (rw[list(blocked)] == 0).all()
+    for q in (1, 98, 101, 148, 151, 198, 201, 298):
+        exp, erw = _oracle(oracle_mod, raw, tuple(starts[q]), int(seeds[q]), 40, 0, 0.0)
+        _assert_same(b.tree(q), exp)
+        assert rw[q] == erw
+
+
 def test_star_large_tree_uncached_knn(pkg, oracle_mod, ctx):
     """a tree past the kNN's LDS distance cache (n > 2048 nodes): the exclusion rounds over global
     memory, plus k at its cap region"""
