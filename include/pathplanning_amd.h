@@ -32,7 +32,8 @@ extern "C" {
  *    (always 0, the layout kept); pp_batch_set_finish_schedule replaces the library's former
  *    environment knobs
  * 5: pp_rrt_extend_samples and pp_rrt_tree_import (the host owns the RNG and the tree); nothing
- *    else changed */
+ *    else changed
+ * 5 (+): pp_star_plan / pp_star_goal_costs / pp_star_path added, nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -331,6 +332,32 @@ int pp_star_state(pp_ctx* ctx, int32_t* n_nodes, int64_t* iterations, int64_t* n
 /* one query's tree (root first): coordinates, yaw, parent (-1 root) and node cost (root 0) */
 int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* yaw,
                         int32_t* parent, double* cost, int64_t cap, int64_t* n);
+/* Goal connection (build-defined; CPU restatement tests/star_goal_ref.py).  The
+ * goal edge of tree node m: the goal (gx, gy, gyaw) is the child and keeps its yaw, node m is the
+ * parent — Dubins from the goal pose to the node's stored pose; feasible when the word is Some and
+ * Space::verify accepts the edge's points followed by the node's point.  total[m] = cost[m] + the
+ * edge's Dubins cost (the unit of pp_star_tree_export's cost), +inf when infeasible; the root is a
+ * candidate like any other.  The best node is the first strict minimum of total in node order
+ * (the lowest index on an exact tie).
+ *
+ * goal connection of every query of the RRT* batch on its tree as extended so far.
+ * goals: q rows (gx, gy, gyaw).  Per query (each may be NULL): best_node (-1 none), cost (+inf none);
+ * *n_checked = the (query, node) pairs considered = sum of tree sizes.  Trees are not modified;
+ * may be called again after more pp_star_extend steps or with other goals. */
+int pp_star_plan(pp_ctx* ctx, const double* goals, int32_t* best_node, double* cost,
+                 int64_t* n_checked);
+/* un-pruned cost-to-goal of one query: total[m] = cost[m] + e[m] or +inf, m < *n (cap as in the
+ * exports: PP_ERR_CAPACITY when cap < *n; total NULL: the size only) */
+int pp_star_goal_costs(pp_ctx* ctx, int query, const double goal[3], double* total, int64_t cap,
+                       int64_t* n);
+/* the path of (query, goal, node), root first: with E(child, parent) the kept Dubins points of
+ * the edge from the child's stored pose to the parent's stored pose (a rewired node keeps its
+ * pose), the line E(goal, node) ++ E(node, parent[node]) ++ ... ++ E(., root) ++ [(x0, y0)],
+ * reversed; *length = its euclidean_length.  cap 0 or NULL x/y: the size only; PP_ERR_CAPACITY
+ * when too small; PP_ERR_INVALID_ARGUMENT for a node out of range or whose goal edge is
+ * infeasible; PP_ERR_REFERENCE_PANIC when a tree edge of the chain has no Dubins word */
+int pp_star_path(pp_ctx* ctx, int query, const double goal[3], int32_t node, double* x, double* y,
+                 int64_t cap, int64_t* n, double* length);
 
 int pp_rrt_get_stats(pp_ctx* ctx, pp_stats* out, uint64_t out_size);
 int pp_rrt_reset_stats(pp_ctx* ctx);

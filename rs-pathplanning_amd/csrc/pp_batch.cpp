@@ -289,7 +289,9 @@ int star_k(int k_fixed, int n) {
     return k < n ? k : n;
 }
 
-StarArgs star_args(pp_ctx* c) {
+}  // namespace
+
+StarArgs ppamd::star_args(pp_ctx* c) {
     const StarBatch& s = c->star;
     StarArgs a;
     StarDev& d = a.sd;
@@ -338,6 +340,8 @@ StarArgs star_args(pp_ctx* c) {
     a.wg_points = c->prof.points();
     return a;
 }
+
+namespace {
 
 // Sub-batch s of the RRT* batch (as mq_sub_args): the forest's view of its queries, RRT*'s own
 // per-query and per-row arrays, its own round states and task regions (rounds B / C: kStarKMax

@@ -5,6 +5,7 @@
 //   pp_rrt.cpp      the one-tree planner and its window buffers
 //   pp_finish.cpp   check_finish / optimize / finalize, pp_rrt_plan, pp_batch_plan
 //   pp_batch.cpp    the forest of per-query trees, pp_batch_*, pp_star_*
+//   pp_star_goal.cpp  the RRT* goal connection: pp_star_plan, pp_star_goal_costs, pp_star_path
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -378,6 +379,11 @@ struct StarBatch {
     DBuf<int> sA, sB, sC;
     DBuf<double> yA, yB, yC, cA, cB, cC;
     DBuf<PrepRec> rec;
+    // the goal connection (pp_star_plan / pp_star_goal_costs: StarGoalArgs), reserved on first use
+    DBuf<double> goal_d, gbest, gtotal;
+    DBuf<int> gslot, gnode;
+    DBuf<uint64_t> gmask;
+    DBuf<long long> gsteer;
 };
 
 // ---- profiling
@@ -444,5 +450,7 @@ int check_ctx(pp_ctx* c, bool need_scene, bool need_rrt);
 int ensure_events(pp_ctx* c, size_t count);
 // reserve the API literal scratch pool and (once, zeroed on `st`) its slot locks
 int ensure_literal_pool(pp_ctx* c, hipStream_t st);
+// the RRT* batch's kernel arguments, the whole batch's view (pp_batch.cpp)
+StarArgs star_args(pp_ctx* c);
 
 }  // namespace ppamd

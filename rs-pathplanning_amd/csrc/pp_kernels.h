@@ -241,6 +241,24 @@ struct StarArgs {
 hipError_t launch_star_steps(hipStream_t s, const StarArgs& a, int steps);
 hipError_t launch_star_init(hipStream_t s, const StarArgs& a, const double* starts);
 
+// RRT* goal connection (pp_star_plan / pp_star_goal_costs): `rounds` rounds of 63 nodes per query
+// over the queries [q0, q1) of the batch `a` views, which lends round B's task arrays, the records
+// and stB->W.  Per query: best (+inf none) and best_node (-1 none), the first strict minimum of
+// cost(m) + the goal edge's Dubins cost over the feasible nodes.
+struct StarGoalArgs {
+    StarArgs a;
+    int q0 = 0, q1 = 0;
+    const double* goals = nullptr;  // [3 * queries of the batch] (gx, gy, gyaw)
+    int* gslot = nullptr;           // [queries] first task of the query in the current round
+    uint64_t* gmask = nullptr;      // [queries] lanes (nodes of the slice) with a task
+    double* best = nullptr;         // [queries] the running best
+    int* best_node = nullptr;
+    long long* steered = nullptr;   // the tasks emitted over all rounds (the cull's effect)
+    int prune = 1;                  // 0: every node gets a task and no cull limit (the un-pruned costs)
+    double* total = nullptr;        // q1 == q0 + 1: total[m] of that query's nodes (or null)
+};
+hipError_t launch_star_goal(hipStream_t s, const StarGoalArgs& g, int rounds);
+
 // dubins_path_planning_from_origin for n (dx, dy, eyaw, c, step_size) configurations
 hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int cap, double* px,
                                 double* py, double* pyaw, int* n_out, int* word_out,

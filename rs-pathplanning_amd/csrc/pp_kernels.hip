@@ -5788,6 +5788,168 @@ hipError_t launch_star_init(hipStream_t s, const StarArgs& a, const double* star
     return hipGetLastError();
 }
 
+// ------------------------------------------------ RRT* goal connection (pp_star_plan, §3.7)
+//
+// The cheapest feasible goal edge of every query (oracle restatement: tests/star_goal_ref.py).
+// The goal is the child and keeps its yaw, node m is the parent, total(m) = cost(m) + the edge's
+// Dubins cost.  Round r serves node slice [63 r, 63 r + 63) of every query in [q0, q1):
+//   star_goal_emit    one wave per query: one task per node of the slice whose chord lower bound
+//                     stays under the query's running best, written compactly into round B's
+//                     task arrays (stB->W counts them)
+//   steer_prep / steer_walk   the extend's round, cull limit = the running best
+//   star_goal_reduce  one wave per query: the slice's first strict minimum, which replaces the
+//                     running best only when strictly smaller — so the result is the first
+//                     strict minimum in node order, and a pruned or culled node (total >= the
+//                     running best) could never have replaced it
+// The trees and the extend's own state are only read; round B's arrays, the records and stB->W
+// are rewritten by every extend step before it reads them (star_sample zeroes stB->W).
+__global__ __launch_bounds__(256) void star_goal_init_kernel(StarGoalArgs g) {
+    const int q = g.q0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q == g.q0) {
+        g.a.sd.stB->W = 0;
+        *g.steered = 0;
+    }
+    if (q >= g.q1) return;
+    g.best[q] = __builtin_inf();
+    g.best_node[q] = -1;
+}
+
+__global__ __launch_bounds__(256) void star_goal_emit_kernel(StarGoalArgs g, int round) {
+    const StarDev& sd = g.a.sd;
+    const MqDev& mq = sd.mq;
+    const int lane = __lane_id(), wave = threadIdx.x >> 6;
+    __shared__ int s_cnt[4], s_base;
+    // every wave of a workgroup runs the same iterations (queries q0 + b * 4 + w, + the grid's
+    // stride), so the task reservation is one atomic per workgroup (as star_knn / star_insert)
+    for (int qb = g.q0 + (int)blockIdx.x * 4; qb < g.q1; qb += (int)gridDim.x * 4) {
+        const int q = qb + wave;
+        const bool live = q < g.q1;
+        const size_t row = (size_t)(live ? q : 0) * mq.cap;
+        const int n = live ? mq.n[q] : 0;
+        const int m = 63 * round + lane;  // (lane 63 idles: kStarKMax task slots per query)
+        const bool has = lane < kStarKMax && m < n;
+        // polygon mode: a blocked root's tree is the root alone and no line through it verifies
+        bool want = has && !(mq.blocked && mq.blocked[q]);
+        double gx = 0.0, gy = 0.0, gyaw = 0.0, best = 0.0, cm = 0.0;
+        if (live) {
+            gx = g.goals[3 * (size_t)q];
+            gy = g.goals[3 * (size_t)q + 1];
+            gyaw = g.goals[3 * (size_t)q + 2];
+            best = g.best[q];
+        }
+        if (has && g.total) g.total[m] = __builtin_inf();
+        if (want) {
+            cm = sd.cost[row + m];
+            if (g.prune) {  // the chord lower bound already reaches the running best
+                const double dx = gx - mq.x[row + m], dy = gy - mq.y[row + m];
+                want = cm + star_chord_lb(dx * dx + dy * dy, sd.curv) < best;
+            }
+        }
+        const uint64_t bm = __ballot(want);
+        const int cnt = __popcll(bm);
+        if (lane == 0) s_cnt[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int tot = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            s_base = tot > 0 ? atomicAdd(&sd.stB->W, tot) : 0;
+        }
+        __syncthreads();
+        if (live) {
+            int slot = s_base;
+            for (int w = 0; w < wave; ++w) slot += s_cnt[w];
+            if (lane == 0) {
+                g.gslot[q] = cnt > 0 ? slot : 0;
+                g.gmask[q] = bm;
+            }
+            if (want) {  // node order
+                const int t = slot + __popcll(bm & ((1ull << lane) - 1ull));
+                SteerTask tk{};
+                tk.x = gx;
+                tk.y = gy;
+                tk.px = mq.x[row + m];
+                tk.py = mq.y[row + m];
+                tk.pyaw = mq.yaw[row + m];
+                tk.pnode = m;
+                g.a.tB[t] = tk;
+                StarTaskExt ex{};
+                ex.cyaw = gyaw;
+                ex.own_yaw = 1;
+                ex.node = m;
+                ex.cull = g.prune;  // only a total strictly under the running best matters
+                ex.cbase = cm;
+                ex.climit = best;
+                g.a.eB[t] = ex;
+            }
+        }
+        __syncthreads();  // s_cnt / s_base are rewritten by the next iteration
+    }
+}
+
+__global__ __launch_bounds__(256) void star_goal_reduce_kernel(StarGoalArgs g, SceneDev sc) {
+    const StarDev& sd = g.a.sd;
+    const int lane = __lane_id();
+    const int gw = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int nw = (int)((gridDim.x * blockDim.x) >> 6);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {  // the round's walk is done: the next round's count
+        *g.steered += sd.stB->W;
+        sd.stB->W = 0;
+    }
+    for (int q = g.q0 + gw; q < g.q1; q += nw) {
+        const uint64_t bm = g.gmask[q];
+        if (!bm) continue;
+        const bool act = lane < __popcll(bm);
+        SteerTask tk{};
+        StarTaskExt ex{};
+        int st = kReject;
+        double e = __builtin_inf();
+        if (act) {
+            const int t = g.gslot[q] + lane;
+            tk = g.a.tB[t];
+            ex = g.a.eB[t];
+            st = g.a.sB[t];
+            e = g.a.cB[t];
+        }
+        st = star_settle(sc, st, act, tk.x, tk.y, ex.cyaw, tk.px, tk.py, tk.pyaw, g.a.lit_scratch,
+                         sd.lit_locks, gw);
+        if (__ballot(act && st == kError)) {  // n_point overflow: the reference panics
+            if (lane == 0) atomicOr(g.a.err, 1);
+            continue;
+        }
+        double c = act && star_feasible(st, e) ? ex.cbase + e : __builtin_inf();
+        if (act && g.total) g.total[ex.node] = c;
+        int bl = lane;
+        wave_argmin(c, bl);  // the lowest lane (node) on ties
+        const int node = __shfl(ex.node, bl);
+        if (lane == 0 && c < g.best[q]) {
+            g.best[q] = c;
+            g.best_node[q] = node;
+        }
+    }
+}
+
+hipError_t launch_star_goal(hipStream_t s, const StarGoalArgs& g, int rounds) {
+    const StarArgs& a = g.a;
+    const int Q = g.q1 - g.q0;
+    const int TB = Q * kStarKMax;  // a round's task capacity: 63 per query
+    const int qb = std::min((Q + 3) / 4, 4096);
+    const int prep = std::min((TB + kPrepThreads / 8 - 1) / (kPrepThreads / 8), 2048);
+    // (the walk grid of launch_star_steps' rounds B and C)
+    const int walk_cap = a.sc.lds_bytes > 0
+                             ? std::min(kWalkMaxWG, walk_grid_cap<kWalkMinWStar, 4, true>(a.sc))
+                             : 1024;
+    const int walk = std::min((TB + kWalkThreads / 64 - 1) / (kWalkThreads / 64), walk_cap);
+    star_goal_init_kernel<<<(Q + 255) / 256, 256, 0, s>>>(g);
+    for (int r = 0; r < rounds; ++r) {
+        star_goal_emit_kernel<<<qb, 256, 0, s>>>(g, r);
+        steer_prep_kernel<<<prep, kPrepThreads, 0, s>>>(a.sd.stB, a.sc, nullptr, nullptr, nullptr,
+                                                        nullptr, a.rec, a.yB, a.tB, a.cB, a.eB);
+        launch_walk<kWalkMinWStar, true>(s, walk, a.sd.stB, a.sc, a.rec, nullptr, a.sB, nullptr,
+                                         nullptr, a.wg_points);
+        star_goal_reduce_kernel<<<qb, 256, 0, s>>>(g, a.sc);
+    }
+    return hipGetLastError();
+}
+
 // --------------------------------------------------------------------------- launch wrappers
 
 namespace {

@@ -566,6 +566,7 @@ class RRTStarBatch:
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
         self.q = len(starts)
         self.max_iter = int(max_iter)
+        self.n_checked = 0  # (query, node) pairs of the last plan()
         space._upload(self.ctx)
         _ffi.check(_ffi.lib().pp_star_new(
             self.ctx.handle, self.q, starts.ctypes.data_as(C.POINTER(C.c_double)),
@@ -610,6 +611,54 @@ class RRTStarBatch:
             yaw.ctypes.data_as(dp), par.ctypes.data_as(ip), cost.ctypes.data_as(dp), n,
             C.byref(out)))
         return x, y, yaw, par, cost
+
+    # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path)
+    def plan(self, goals):
+        """The cheapest feasible goal edge of every query on its tree as extended so far: goal
+        (gx, gy, gyaw) per query (one pose is broadcast to all).  Returns (best_node int32[q],
+        cost float64[q]): -1 and inf where no node reaches the goal.  ``n_checked``: the
+        (query, node) pairs considered."""
+        g = np.asarray(goals, dtype=np.float64)
+        g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
+        g = np.ascontiguousarray(g, dtype=np.float64).reshape(self.q, 3)
+        node = np.zeros(self.q, dtype=np.int32)
+        cost = np.zeros(self.q)
+        chk = C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        _ffi.check(_ffi.lib().pp_star_plan(
+            self.ctx.handle, g.ctypes.data_as(dp), node.ctypes.data_as(C.POINTER(C.c_int32)),
+            cost.ctypes.data_as(dp), C.byref(chk)))
+        self.n_checked = chk.value
+        return node, cost
+
+    def goal_costs(self, query: int, goal):
+        """total[m] = cost[m] + the goal edge's Dubins cost of every node of one query (inf where
+        the edge is infeasible), without pruning."""
+        g = np.ascontiguousarray(goal, dtype=np.float64).reshape(3)
+        out = C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        L = _ffi.lib()
+        _ffi.check(L.pp_star_goal_costs(self.ctx.handle, int(query), g.ctypes.data_as(dp), None, 0,
+                                        C.byref(out)))  # (the tree's size)
+        total = np.zeros(out.value)
+        _ffi.check(L.pp_star_goal_costs(self.ctx.handle, int(query), g.ctypes.data_as(dp),
+                                        total.ctypes.data_as(dp), out.value, C.byref(out)))
+        return total
+
+    def path(self, query: int, goal, node: int):
+        """(xy[n, 2], length): the path root -> ... -> node -> goal along the tree's stored poses
+        (``node``: one whose goal edge is feasible, e.g. plan()'s best node)."""
+        g = np.ascontiguousarray(goal, dtype=np.float64).reshape(3)
+        dp = C.POINTER(C.c_double)
+        n, length = C.c_int64(0), C.c_double(0.0)
+        L = _ffi.lib()
+        _ffi.check(L.pp_star_path(self.ctx.handle, int(query), g.ctypes.data_as(dp), int(node),
+                                  None, None, 0, C.byref(n), None))
+        x, y = np.zeros(n.value), np.zeros(n.value)
+        _ffi.check(L.pp_star_path(self.ctx.handle, int(query), g.ctypes.data_as(dp), int(node),
+                                  x.ctypes.data_as(dp), y.ctypes.data_as(dp), n.value, C.byref(n),
+                                  C.byref(length)))
+        return np.stack([x, y], axis=1), length.value
 
     def close(self):
         self.ctx.close()
