@@ -223,7 +223,7 @@ MqArgs mq_args(pp_ctx* c) {
 
 // Sub-batch s of the batch: the forest's view of its queries, the window arrays' task regions
 // (K slots per query) and its own DevState.
-constexpr size_t kLstatPad = 1024;  // >= the walk's grid (kWalkMaxWG)
+constexpr size_t kLstatPad = 1024;  // >= the walk's grid (kWalkMaxWG, pp_steer_launch.h)
 MqArgs mq_sub_args(pp_ctx* c, int sub) {
     const Batch& b = c->batch;
     MqArgs a = mq_args(c);

@@ -1,4 +1,5 @@
-// pp_kernels.h — host-side launch wrappers of the HIP kernels (pp_kernels.hip).
+// pp_kernels.h — host-side launch wrappers of the HIP kernels (pp_kernels.hip; the API kernels'
+// wrappers: pp_k_steer.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -25,7 +25,7 @@ constexpr int kLiteralWaves = 256;   // literal scratch buffers (explicit-task k
 constexpr int kResolveThreads = 512;  // resolve_tail_kernel (8 waves, 256 VGPRs: the repair path)
 constexpr int kMaxWindow = 4096;     // K limit: the resolve keeps the window's state in LDS
 constexpr int kMinDynWindow = 128;   // the adaptive window's floor (DevState.kdyn)
-constexpr int kSteerPrepBytes = 152; // sizeof(SteerPrep) (checked in pp_kernels.hip)
+constexpr int kSteerPrepBytes = 152; // sizeof(SteerPrep) (checked in pp_steer_dev.h)
 constexpr int kPrepLanes = 8;        // lanes per task in steer_prep's phase A
 constexpr int kPrepThreads = 256;    // steer_prep workgroup: 32 tasks (8 per wave)
 constexpr int kWalkThreads = 512;    // steer_walk workgroup: 8 tasks at a time (3 workgroups per CU)

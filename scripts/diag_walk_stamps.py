@@ -37,10 +37,12 @@ extern "C" unsigned ppdiag_count() { return 128; }
 # [5] chunk_rejects items cycles [6] chunks [7] wave span cycles (first task start .. exit)
 # [30] generate cycles [31] chunk_rejects setup cycles (bounds, bbox, cells)
 # [8..31] per-task cycle histogram, bin = floor(log2(cycles)) - 8; [32..63] chunks per task (31: more)
+# (file, text, replacement): D the shared device header, K the unit that owns steer_walk_kernel
+D, K = "pp_steer_dev.h", "pp_k_steer.hip"
 PATCHES_K = [
-    ("extern __shared__ __attribute__((aligned(16))) char pp_smem[];",
+    (D, "extern __shared__ __attribute__((aligned(16))) char pp_smem[];",
      "extern __shared__ __attribute__((aligned(16))) char pp_smem[];\n" + KERNEL_DECL),
-    ("""    const int ncx = cx1 - cx0 + 1, ncy = cy1 - cy0 + 1;
+    (D, """    const int ncx = cx1 - cx0 + 1, ncy = cy1 - cy0 + 1;
     if (ncx <= 0 || ncy <= 0) return false;""",
      """    const int ncx = cx1 - cx0 + 1, ncy = cy1 - cy0 + 1;
     if (g_diag && lane == 0) {
@@ -48,24 +50,24 @@ PATCHES_K = [
         atomicAdd(g_diag + 64 + (nc < 31 ? nc : 31), 1ull);
     }
     if (ncx <= 0 || ncy <= 0) return false;"""),
-    ("""            if (items_reject(kk >= 0, kk)) return true;
+    (D, """            if (items_reject(kk >= 0, kk)) return true;
             if (mb + 64 >= run) break;""",
      """            if (g_diag && lane == 0 && mb == 0) atomicAdd(g_diag + 96 + (run < 31 ? run : 31), 1ull);
             if (items_reject(kk >= 0, kk)) return true;
             if (mb + 64 >= run) break;"""),
 
-    ("""__device__ __forceinline__ bool chunk_rejects(const SceneDev& sc, bool has, bool check_bounds,
+    (D, """__device__ __forceinline__ bool chunk_rejects(const SceneDev& sc, bool has, bool check_bounds,
                                               bool seg_valid, double qx, double qy) {""",
      """__device__ __forceinline__ bool chunk_rejects(const SceneDev& sc, bool has, bool check_bounds,
                                               bool seg_valid, double qx, double qy,
                                               long long* dgc = nullptr) {"""),
-    ("""    auto items_reject = [&](bool valid, int kk) -> bool {""",
+    (D, """    auto items_reject = [&](bool valid, int kk) -> bool {""",
      """    if (dgc) {
         __builtin_amdgcn_s_waitcnt(0);
         dgc[0] = __builtin_amdgcn_s_memtime();
     }
     auto items_reject = [&](bool valid, int kk) -> bool {"""),
-    ("""        const bool junction_here = done && cnt < 63;""",
+    (D, """        const bool junction_here = done && cnt < 63;""",
      """        if (dg) {
             __builtin_amdgcn_s_waitcnt(0);
             const long long t = __builtin_amdgcn_s_memtime();
@@ -73,7 +75,7 @@ PATCHES_K = [
             dt0 = t;
         }
         const bool junction_here = done && cnt < 63;"""),
-    ("""                                        int& npts, int& napts, bool junction = true) {
+    (D, """                                        int& npts, int& napts, bool junction = true) {
     const int lane = threadIdx.x & 63;
     const int state = p->state;
     const double x = p->x, y = p->y, px = p->px, py = p->py;""",
@@ -89,7 +91,7 @@ PATCHES_K = [
         dg[0] += t - dt0 + (state & 0);
         dt0 = t;
     }"""),
-    ("""        const bool has = lane == 0 || isgrid || isj;
+    (D, """        const bool has = lane == 0 || isgrid || isj;
         const bool chk = isgrid || isj || (base == 0 && lane == 0);""",
      """        if (dg) {
             __builtin_amdgcn_s_waitcnt(0);
@@ -100,7 +102,7 @@ PATCHES_K = [
         }
         const bool has = lane == 0 || isgrid || isj;
         const bool chk = isgrid || isj || (base == 0 && lane == 0);"""),
-    ("""        if (chunk_rejects<kLds, kScene>(sc, has, chk, has && lane >= 1, qx, qy)) return kReject;
+    (D, """        if (chunk_rejects<kLds, kScene>(sc, has, chk, has && lane >= 1, qx, qy)) return kReject;
         if (junction_here) break;""",
      """        long long dgc[1] = {0};
         const bool rj = chunk_rejects<kLds, kScene>(sc, has, chk, has && lane >= 1, qx, qy,
@@ -117,7 +119,7 @@ PATCHES_K = [
         }
         if (rj) return kReject;
         if (junction_here) break;"""),
-    ("""    __shared__ int s_next;
+    (K, """    __shared__ int s_next;
     const int G = (int)gridDim.x;
     if (threadIdx.x == 0) s_next = 0;
     __syncthreads();
@@ -164,7 +166,7 @@ PATCHES_K = [
             const int ch = (int)(dg[3] < 31 ? dg[3] : 31);
             for (int i = 0; i < 32; ++i) dcn[i] += (i == ch);
         }"""),
-    ("""    if (wg_points) {  // [b]: points, [kWalkTallySlots + b]: their arc points""",
+    (K, """    if (wg_points) {  // [b]: points, [kWalkTallySlots + b]: their arc points""",
      """    if (g_diag && lane == 0 && dsum[0] > 0) {
         dsum[7] = __builtin_amdgcn_s_memtime() - dfirst;
         for (int i = 0; i < 8; ++i) atomicAdd(g_diag + i, (unsigned long long)dsum[i]);
@@ -240,7 +242,7 @@ def build():
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(BUILD, "include"))
     for f in ge.SOURCES + ge.HEADERS:
         shutil.copy(os.path.join(SRC, f), csrc)
-    patches = [("pp_kernels.hip", a, b) for a, b in PATCHES_K] + PATCHES_C
+    patches = PATCHES_K + PATCHES_C
     for name in sorted({p[0] for p in patches}):
         p = os.path.join(csrc, name)
         s = open(p).read()

@@ -42,9 +42,11 @@ extern "C" unsigned pptl_count() {
 }
 """
 
+# all in the unit that owns steer_walk_kernel
+KERNEL_FILE = "pp_k_steer.hip"
 PATCHES_K = [
-    ("extern __shared__ __attribute__((aligned(16))) char pp_smem[];",
-     "extern __shared__ __attribute__((aligned(16))) char pp_smem[];\n" + KERNEL_DECL),
+    ("__host__ __device__ inline int walk_lds_bytes(int scene_bytes) {",
+     KERNEL_DECL + "\n__host__ __device__ inline int walk_lds_bytes(int scene_bytes) {"),
     ("""    const bool t0 = threadIdx.x == 0;
     if (kLds) stage_scene(sc);""",
      """    const bool t0 = threadIdx.x == 0;
@@ -177,7 +179,7 @@ def build():
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(BUILD, "include"))
     for f in ge.SOURCES + ge.HEADERS:
         shutil.copy(os.path.join(SRC, f), csrc)
-    patches = [("pp_kernels.hip", a, b) for a, b in PATCHES_K] + PATCHES_C
+    patches = [(KERNEL_FILE, a, b) for a, b in PATCHES_K] + PATCHES_C
     for name in sorted({p[0] for p in patches}):
         p = os.path.join(csrc, name)
         s = open(p).read()

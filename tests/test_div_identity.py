@@ -1,4 +1,4 @@
-"""CPU: the walk's division by the curvature (walk_rec, csrc/pp_kernels.hip div_by) and mod2pi's
+"""CPU: the walk's division by the curvature (walk_rec, csrc/pp_steer_dev.h; div_by) and mod2pi's
 division by 2pi (csrc/pp_device.h) are bit-identical to IEEE division.  interpolate (dubins.rs:169-178) divides every point's length, sin and 1 - cos by
 max_curvature c; the walk computes x / c as q = RN(x rc), then RN(q + fma(-q, c, x) rc) with
 rc = RN(1 / c) — Markstein's correctly rounded quotient.  Checked here in C (gcc, FMA as the

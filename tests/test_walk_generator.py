@@ -1,4 +1,4 @@
-"""The lane-parallel `pd += d` generator of steer_walk (pp_kernels.hip, walk_rec) restated with
+"""The lane-parallel `pd += d` generator of steer_walk (pp_steer_dev.h, walk_rec) restated with
 numpy lanes and checked against the serial walk of generate_local_course (dubins.rs:239-259):
 same points, same segment split, same values bit for bit.  CPU only (algorithm check; the HIP
 kernel itself is covered by the GPU parity tests)."""
