@@ -33,7 +33,8 @@ extern "C" {
  *    environment knobs
  * 5: pp_rrt_extend_samples and pp_rrt_tree_import (the host owns the RNG and the tree); nothing
  *    else changed
- * 5 (+): pp_star_plan / pp_star_goal_costs / pp_star_path added, nothing else changed */
+ * 5 (+): pp_star_plan / pp_star_goal_costs / pp_star_path added, nothing else changed
+ * 5 (+): pp_batch_paths / pp_star_paths added, nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -303,6 +304,22 @@ int pp_batch_state(pp_ctx* ctx, int32_t* n_nodes, int64_t* iterations, int64_t* 
  * (query, node) pairs checked. */
 int pp_batch_plan(pp_ctx* ctx, int32_t* best_node, double* length, int32_t* n_points,
                   int32_t* n_finishes, int64_t* n_checked);
+/* Every query's planned line in one call, packed.  finalize's line (rrt.rs:503-540) of
+ * check_finish(nodes[i]) for every query i of the batch, with the query's own goal: exactly the
+ * line pp_rrt_check_finish returns for that node on that tree (root side first).  nodes: q
+ * entries, a node of query i's tree (0 .. n_i - 1) or -1 (skip).  off: q + 1 entries, row i =
+ * points [off[i], off[i + 1]) of x / y; a row is empty when nodes[i] is -1 or check_finish is
+ * None (ok[i] = 0).  ok (q, may be NULL).  *n_total = off[q].  With nodes = pp_batch_plan's
+ * best_node, row i has that plan's n_points[i] points, so x / y can be sized from the plan.
+ * x / y NULL or cap <= 0: sizes only (off, ok, n_total filled, PP_OK).  cap < *n_total:
+ * PP_ERR_CAPACITY with off / ok / n_total filled; also when *n_total exceeds what one call stages
+ * on the device, 2^26 points (1 GiB; export the queries in several calls then, -1 skips a query).
+ * PP_ERR_STATE without a batch; PP_ERR_INVALID_ARGUMENT for a NULL nodes, off or n_total or a
+ * node outside its query's tree; the check_finish errors as pp_batch_plan
+ * (PP_ERR_REFERENCE_PANIC, ...).  Runs on the context's stream; the trees and the extend state
+ * are not modified. */
+int pp_batch_paths(pp_ctx* ctx, const int32_t* nodes, int64_t* off, double* x, double* y,
+                   int64_t cap, int64_t* n_total, uint8_t* ok);
 /* one query's tree (root first), like pp_rrt_tree_export */
 int pp_batch_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* yaw,
                          int32_t* parent, int64_t cap, int64_t* n);
@@ -358,6 +375,18 @@ int pp_star_goal_costs(pp_ctx* ctx, int query, const double goal[3], double* tot
  * infeasible; PP_ERR_REFERENCE_PANIC when a tree edge of the chain has no Dubins word */
 int pp_star_path(pp_ctx* ctx, int query, const double goal[3], int32_t node, double* x, double* y,
                  int64_t cap, int64_t* n, double* length);
+/* pp_star_path's line of (query i, goals[3i..], nodes[i]) for every query of the RRT* batch in
+ * one call, packed like pp_batch_paths (rows, off, cap, n_total, ok, -1, the 2^26-point limit):
+ * E(goal, node) ++ E(node, parent) ++ ... ++ [(x0, y0)], reversed.  length (q, may be NULL): the
+ * row's euclidean_length, 0 for an empty row; filled with the points (not by a sizes-only call).
+ * ok[i] = 0 and an empty row when the goal edge has no Dubins word; a tree edge without one is
+ * PP_ERR_REFERENCE_PANIC; a chain deeper than 8192 nodes or a line of more than 65536 points
+ * PP_ERR_CAPACITY.  The goal edge's Space::verify is pp_star_plan's business and is not repeated
+ * here: any node's line is returned.  PP_ERR_STATE without an RRT* batch;
+ * PP_ERR_INVALID_ARGUMENT for a NULL goals, nodes, off or n_total, a non-finite goal or a node
+ * outside its query's tree.  The trees are not modified. */
+int pp_star_paths(pp_ctx* ctx, const double* goals, const int32_t* nodes, int64_t* off, double* x,
+                  double* y, int64_t cap, int64_t* n_total, double* length, uint8_t* ok);
 
 int pp_rrt_get_stats(pp_ctx* ctx, pp_stats* out, uint64_t out_size);
 int pp_rrt_reset_stats(pp_ctx* ctx);

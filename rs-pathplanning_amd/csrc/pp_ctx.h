@@ -3,9 +3,10 @@
 //   pp_context.cpp  context, errors, statistics, profiling, the Dubins entry points
 //   pp_space.cpp    the scene
 //   pp_rrt.cpp      the one-tree planner and its window buffers
-//   pp_finish.cpp   check_finish / optimize / finalize, pp_rrt_plan, pp_batch_plan
+//   pp_finish.cpp   check_finish / optimize / finalize, pp_rrt_plan, pp_batch_plan, pp_batch_paths
 //   pp_batch.cpp    the forest of per-query trees, pp_batch_*, pp_star_*
-//   pp_star_goal.cpp  the RRT* goal connection: pp_star_plan, pp_star_goal_costs, pp_star_path
+//   pp_star_goal.cpp  the RRT* goal connection: pp_star_plan, pp_star_goal_costs, pp_star_path,
+//                     pp_star_paths
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -286,6 +287,17 @@ struct Finish {
     DBuf<double> len, pts;
 };
 
+// ---- packed line export (pp_batch_paths / pp_star_paths): the call's items, counts, row
+// offsets and the packed points, sized to the call
+struct PathExport {
+    DBuf<int> qidx, nodes, slot, ok, cnt, items;
+    DBuf<double> len, x, y;
+    DBuf<int64_t> off;
+    DBuf<uint8_t> okq;
+};
+// the most points one export call stages on the device (x and y: 16 B a point, 1 GiB)
+constexpr int64_t kPathsMaxPoints = (int64_t)1 << 26;
+
 // ---- a forest of per-query SoA trees: the host side of MqDev's shared part, under both the
 // extend batch (config 3) and the RRT* batch (config 5).  Tree q lives in rows [q * cap, q * cap +
 // n[q]); the forest runs as nsub sub-batches of consecutive queries, each on its own stream.
@@ -431,6 +443,7 @@ struct pp_ctx {
     ppamd::Finish cf;
     ppamd::Batch batch;
     ppamd::StarBatch star;
+    ppamd::PathExport paths;
     ppamd::Profiling prof;
 
     // the scene as the one-tree planner's kernels see it (its step, its blocked root)
@@ -452,5 +465,19 @@ int ensure_events(pp_ctx* c, size_t count);
 int ensure_literal_pool(pp_ctx* c, hipStream_t st);
 // the RRT* batch's kernel arguments, the whole batch's view (pp_batch.cpp)
 StarArgs star_args(pp_ctx* c);
+// The steps pp_batch_paths and pp_star_paths share (pp_finish.cpp).  paths_items: the call's
+// (query, node) items from nodes[0, Q) (-1: skipped; sizes: the trees' node counts) into
+// paths.qidx / nodes / slot on the device, *k their count.  paths_sizes: the rows' offsets from
+// paths.cnt / ok by the scan, to the caller (off, ok, n_total), and the capacity checks; *go:
+// the caller wants the points and there are some.  paths_write: the write pass over `items`
+// into paths.x / y and their copy to x / y (and of the k items' lengths, paths.len, to len_host),
+// then one synchronise.
+int paths_items(pp_ctx* c, const Forest& f, const int32_t* nodes, int* k);
+int paths_sizes(pp_ctx* c, int Q, int64_t* off, const double* x, const double* y, int64_t cap,
+                int64_t* n_total, uint8_t* ok, bool* go);
+int paths_line_buffers(pp_ctx* c, int k, CfLines& lines);
+int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines,
+                const int* items, int k, bool star, double* x, double* y, int64_t total,
+                double* len_host = nullptr);
 
 }  // namespace ppamd

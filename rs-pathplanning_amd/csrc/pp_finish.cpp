@@ -1,5 +1,6 @@
 // pp_finish.cpp — RRT::check_finish / optimize / finalize of the one-tree planner, pp_rrt_plan, and
-// the query batch's plan (pp_batch_plan) over the same kernels.
+// the query batch's plan (pp_batch_plan) over the same kernels; the packed line export of a batch
+// (pp_batch_paths) and the steps it shares with pp_star_paths.
 #include "pp_ctx.h"
 
 using namespace ppamd;
@@ -375,7 +376,142 @@ int cf_copy_line(pp_ctx* c, int E, double* x, double* y, int64_t* n) {
 
 }  // namespace
 
+namespace ppamd {
+
+int paths_items(pp_ctx* c, const Forest& f, const int32_t* nodes, int* k) {
+    const int Q = f.Q;
+    hipStream_t st = c->stream;
+    std::vector<int> hn(Q), qi, nd, slot(Q, -1);
+    PP_HIP(hipMemcpyAsync(hn.data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < Q; ++q) {
+        if (nodes[q] == -1) continue;
+        if (nodes[q] < 0 || nodes[q] >= hn[q])
+            return set_err(PP_ERR_INVALID_ARGUMENT, "node index outside its query's tree");
+        slot[q] = (int)qi.size();
+        qi.push_back(q);
+        nd.push_back(nodes[q]);
+    }
+    *k = (int)qi.size();
+    PathExport& pe = c->paths;
+    PP_HIP(pe.qidx.reserve(Q));
+    PP_HIP(pe.nodes.reserve(Q));
+    PP_HIP(pe.slot.reserve(Q));
+    PP_HIP(pe.ok.reserve(Q));
+    PP_HIP(pe.cnt.reserve(Q));
+    PP_HIP(pe.len.reserve(Q));
+    PP_HIP(pe.off.reserve((size_t)Q + 1));
+    PP_HIP(pe.okq.reserve(Q));
+    // (pageable sources: the copies are complete when the calls return)
+    PP_HIP(hipMemcpyAsync(pe.slot.p, slot.data(), Q * sizeof(int), hipMemcpyHostToDevice, st));
+    if (*k > 0) {
+        PP_HIP(hipMemcpyAsync(pe.qidx.p, qi.data(), *k * sizeof(int), hipMemcpyHostToDevice, st));
+        PP_HIP(hipMemcpyAsync(pe.nodes.p, nd.data(), *k * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    PP_HIP(hipStreamSynchronize(st));
+    return PP_OK;
+}
+
+int paths_sizes(pp_ctx* c, int Q, int64_t* off, const double* x, const double* y, int64_t cap,
+                int64_t* n_total, uint8_t* ok, bool* go) {
+    PathExport& pe = c->paths;
+    hipStream_t st = c->stream;
+    *go = false;
+    PP_HIP(launch_paths_scan(st, Q, pe.slot.p, pe.ok.p, pe.cnt.p, pe.off.p, pe.okq.p));
+    PP_HIP(hipMemcpyAsync(off, pe.off.p, ((size_t)Q + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (ok) PP_HIP(hipMemcpyAsync(ok, pe.okq.p, Q, hipMemcpyDeviceToHost, st));
+    // the one host round trip before the points: the staging and the capacity check need the total
+    PP_HIP(hipStreamSynchronize(st));
+    const int64_t total = off[Q];
+    *n_total = total;
+    if (!x || !y || cap <= 0 || total == 0) return PP_OK;  // the sizes only
+    if (total > kPathsMaxPoints)
+        return set_err(PP_ERR_CAPACITY, "the batch's lines exceed one call's staging (2^26 points): "
+                                        "export the queries in several calls (nodes = -1 skips one)");
+    if (cap < total) return set_err(PP_ERR_CAPACITY, "x / y smaller than the lines' total (n_total)");
+    *go = true;
+    return PP_OK;
+}
+
+int paths_line_buffers(pp_ctx* c, int k, CfLines& lines) {
+    const int wgs = std::min(kCfLineGrid, k);
+    return cf_line_buffers(c, wgs, wgs > 1 ? std::min(k, kCfSpillCap) : 0, lines);
+}
+
+int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines,
+                const int* items, int k, bool star, double* x, double* y, int64_t total,
+                double* len_host) {
+    PathExport& pe = c->paths;
+    hipStream_t st = c->stream;
+    PP_HIP(pe.x.reserve((size_t)total));
+    PP_HIP(pe.y.reserve((size_t)total));
+    a.off = pe.off.p;
+    a.ox = pe.x.p;
+    a.oy = pe.y.p;
+    PP_HIP(c->cf.err.reserve(2));
+    PP_HIP(hipMemsetAsync(c->cf.err.p, 0, 2 * sizeof(int), st));
+    PP_HIP(launch_paths(st, sd, a, lines, c->cf.err.p, items, k, star, true));
+    int err = 0;
+    PP_HIP(hipMemcpyAsync(&err, c->cf.err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(x, pe.x.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(y, pe.y.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (len_host)
+        PP_HIP(hipMemcpyAsync(len_host, pe.len.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    if (err & 16) return set_err(PP_ERR_STATE, "packed export: a line's size changed between the passes");
+    return cf_error(err);
+}
+
+}  // namespace ppamd
+
 extern "C" {
+
+int pp_batch_paths(pp_ctx* ctx, const int32_t* nodes, int64_t* off, double* x, double* y,
+                   int64_t cap, int64_t* n_total, uint8_t* ok) {
+    int r = check_ctx(ctx, true, false);
+    if (r) return r;
+    Batch& b = ctx->batch;
+    if (!b.valid) return set_err(PP_ERR_STATE, "pp_batch_new has not been called");
+    if (!nodes || !off || !n_total) return set_err(PP_ERR_INVALID_ARGUMENT, "null nodes, off or n_total");
+    const int Q = b.f.Q;
+    hipStream_t st = ctx->stream;
+    PathExport& pe = ctx->paths;
+    int k = 0;
+    if ((r = paths_items(ctx, b.f, nodes, &k))) return r;
+    *n_total = 0;
+    if (k == 0) {
+        std::fill(off, off + Q + 1, (int64_t)0);
+        if (ok) std::fill(ok, ok + Q, (uint8_t)0);
+        return PP_OK;
+    }
+    // check_finish of the k items: every item's verdict, optimize chain (a line item per verified
+    // finish, cf.items) and, from its line pass, the line's point count
+    PP_HIP(b.goal_d.reserve(3 * (size_t)Q));
+    PP_HIP(hipMemcpyAsync(b.goal_d.p, b.goal.data(), 3 * (size_t)Q * sizeof(double),
+                          hipMemcpyHostToDevice, st));
+    CfBatch cb;
+    cb.qidx = pe.qidx.p;
+    cb.row_cap = b.f.cap;
+    cb.goals = b.goal_d.p;
+    cb.blocked = b.f.blocked_dev();
+    const TreeDev tr = b.f.tree_dev();
+    if ((r = cf_run(ctx, tr, pe.nodes.p, k, 1, kCfGrid, CfGoal{0.0, 0.0, 0.0, 0.0},
+                    CfOut{pe.ok.p, pe.len.p, pe.cnt.p, nullptr}, cb)))
+        return r;
+    bool go = false;
+    if ((r = paths_sizes(ctx, Q, off, x, y, cap, n_total, ok, &go)) || !go) return r;
+    CfLines lines;
+    if ((r = paths_line_buffers(ctx, k, lines))) return r;
+    SceneDev sd = ctx->scene_dev();
+    sd.step_size = b.f.step;
+    PathsArgs a;
+    a.tr = tr;
+    a.row_cap = b.f.cap;
+    a.qidx = pe.qidx.p;
+    a.nodes = pe.nodes.p;
+    a.goals = b.goal_d.p;
+    return paths_write(ctx, sd, a, lines, ctx->cf.items.p, k, false, x, y, *n_total);
+}
 
 int pp_rrt_check_finish_batch(pp_ctx* ctx, const int32_t* nodes, int k, uint8_t* ok,
                               double* length, int32_t* n_points, int32_t* chain) {

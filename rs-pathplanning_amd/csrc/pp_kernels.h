@@ -194,6 +194,36 @@ hipError_t launch_check_finish(hipStream_t st, const SceneDev& sc, const SceneDe
 constexpr int kCfWaves = 4;                     // check_finish: waves (nodes in flight) per workgroup
 constexpr int kCfItem = 4 + kCfLevels;          // a line item: b, s, verified, 0, pos[kCfLevels]
 
+// Packed line export (pp_batch_paths / pp_star_paths): the lines of the line items (the layout
+// above; item b = node nodes[b] of query qidx[b] of a forest) into one CSR buffer, every row root
+// side first.  star = false: finalize's chain of a check_finish item (s, pos[] from the item;
+// always the write pass — check_finish's own line pass counted); star = true: pp_star_path's chain
+// goal -> node -> parent -> ... -> root, whose count pass (write = false) fills cnt[b] and okf[b]
+// (0: the goal edge has no word).  The write pass stores row q = [off[q], off[q + 1]) of ox / oy
+// and (len != null) the row's euclidean_length in len[b].  err bits as check_finish's, and 16: a
+// row's size differs from the count pass (nothing is stored).  lines: cf_line_kernel's buffers
+// and tiers, the spill count zeroed before every call; items holds at most k items.
+struct PathsArgs {
+    TreeDev tr{};
+    int row_cap = 0;
+    const int* qidx = nullptr;
+    const int* nodes = nullptr;
+    const double* goals = nullptr;  // [3Q] (gx, gy, gyaw)
+    const int64_t* off = nullptr;   // [Q + 1]
+    double* ox = nullptr;
+    double* oy = nullptr;
+    int* cnt = nullptr;
+    int* okf = nullptr;
+    double* len = nullptr;
+};
+hipError_t launch_paths(hipStream_t st, const SceneDev& sc, const PathsArgs& a,
+                        const CfLines& lines, int* err, const int* items, int k, bool star,
+                        bool write);
+// off[0 .. Q] = the exclusive scan of the queries' point counts (cnt[slot[q]] where slot[q] >= 0
+// and okf[slot[q]], else 0), okq[q] that flag
+hipError_t launch_paths_scan(hipStream_t st, int Q, const int* slot, const int* okf,
+                             const int* cnt, int64_t* off, uint8_t* okq);
+
 // pp_batch_plan: the (query, node) items of the accepted nodes (off: [Q + 1] exclusive scan of
 // n_q - 1), and per query the first minimum length over its items' check_finish results
 hipError_t launch_mq_plan_items(hipStream_t s, int Q, const int* off, int* qidx, int* nodes);

@@ -2534,6 +2534,293 @@ hipError_t launch_check_finish(hipStream_t st, const SceneDev& sc, const SceneDe
     return hipGetLastError();
 }
 
+// ------------------------------------------- packed line export (pp_batch_paths, pp_star_paths)
+//
+// Every query's line in one CSR buffer, root side first.  The line generation is one template
+// over a pose provider — the chain of poses whose consecutive pairs are the line's Dubins edges:
+//   CfChainPoses    finalize's chain (check_finish_kernel's pose(j)): the goal, optimize's copies,
+//                   the tree path down to the root; the root contributes no point
+//   StarChainPoses  pp_star_path's chain: the goal with its own yaw, then the stored poses of the
+//                   node, its parent, ..., the root (a rewired node keeps its pose, so no edge
+//                   uses compute_yaw); the root's point ends the forward line
+// line_gen runs cf_line_kernel's steps for such a chain on one wave — every edge's word and slot
+// count (cf_npoint_steer, a lane per edge), the slot offsets, the literal points edge by edge
+// (line_edge_wave) into the workgroup's staging, forward order — and paths_kernel either counts
+// the kept points (kWrite false) or copies them, reversed and compact, to the line's packed row:
+// forward point f of npts goes to row[npts - 1 - f], a lane per point of an edge, so consecutive
+// lanes store consecutive addresses.  Items, tiers and the spill list are cf_line_kernel's.
+enum : int { kLgNone = -2, kLgCap = -1, kLgOverflow = -4, kLgNoneGoal = -5 };
+
+struct CfChainPoses {
+    static constexpr bool kRootPoint = false;  // finalize: the root contributes no point
+    static constexpr bool kGoalNoneOk = false;
+    TreeDev tr;
+    const int* path;
+    const int* pos;
+    int D, s, ps;
+    double gx, gy, gyaw;
+    __device__ CfChainPoses(const TreeDev& t, const int* path_, int D_, const int* o,
+                            const int* pos_, const double* goal)
+        : tr(t), path(path_), pos(pos_), D(D_), s(o[1]), gx(goal[0]), gy(goal[1]), gyaw(goal[2]) {
+        ps = s > 0 ? pos[s - 1] : D - 1;
+    }
+    __device__ int edges() const { return 1 + s + ps; }
+    __device__ CfPose pose(int j) const {
+        if (j == 0) return CfPose{gx, gy, gyaw};  // (a batch's goal: gyaw_opt == gyaw)
+        if (j <= s) {
+            const int i = j - 1;
+            const int here = path[i == 0 ? D - 1 : pos[i - 1]];
+            const int to = path[pos[i]];
+            const double x = tr.x[here], y = tr.y[here];
+            return CfPose{x, y, atan2(tr.y[to] - y, tr.x[to] - x)};  // Node::new (compute_yaw)
+        }
+        const int node = path[ps - (j - s - 1)];
+        return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
+    }
+};
+
+struct StarChainPoses {
+    static constexpr bool kRootPoint = true;
+    static constexpr bool kGoalNoneOk = true;  // a goal edge without a word: ok 0, an empty row
+    TreeDev tr;
+    const int* path;
+    int D;
+    double gx, gy, gyaw;
+    __device__ StarChainPoses(const TreeDev& t, const int* path_, int D_, const int*, const int*,
+                              const double* goal)
+        : tr(t), path(path_), D(D_), gx(goal[0]), gy(goal[1]), gyaw(goal[2]) {}
+    __device__ int edges() const { return D; }  // the goal edge, then node -> parent down to the root
+    __device__ CfPose pose(int j) const {
+        if (j == 0) return CfPose{gx, gy, gyaw};
+        const int node = path[D - j];
+        return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
+    }
+};
+
+// The chain's line by the calling wave (all 64 lanes of a one-wave workgroup): the edges' points
+// in forward order in px / py, et[2e] / et[2e + 1] = edge e's offset there and kept count; pyw
+// holds the words (4 doubles an edge).  Returns the kept points of all edges, or kLg*: a None
+// steer (kLgNoneGoal: the goal edge alone), more slots than pts_cap, an n_point overflow.
+template <class P>
+__device__ int line_gen(const SceneDev& sc, const P& p, int E, double* px, double* py,
+                        double* pyw, int* et, int pts_cap, int lane) {
+    int total = 0;
+    bool none = false, none0 = false;
+    for (int e0 = 0; e0 < E; e0 += 64) {
+        const int e = e0 + lane;
+        int c = 0;
+        if (e < E) {
+            Steer w;
+            c = cf_npoint_steer(sc, p.pose(e), p.pose(e + 1), w);
+            double* wd = pyw + 4 * (size_t)e;
+            wd[0] = (double)w.word;
+            wd[1] = w.t;
+            wd[2] = w.p;
+            wd[3] = w.q;
+        }
+        const uint64_t nm = __ballot(e < E && c == 0);
+        if (nm) {
+            none0 |= e0 == 0 && (nm & 1);
+            none |= (nm & ~(e0 == 0 ? 1ull : 0ull)) != 0;
+        }
+        // (an overflowing count, -1, or one past the capacity: one slot too many for any tier)
+        const int cc = (c < 0 || c > pts_cap) ? pts_cap + 1 : c;
+        const int incl = wave_incl_scan(cc);
+        if (e < E) et[2 * e] = total + incl - cc;
+        total = min(total + __builtin_amdgcn_readlane(incl, 63), pts_cap + 1);
+    }
+    __syncthreads();
+    if (none) return kLgNone;
+    if (none0) return kLgNoneGoal;
+    if (total > pts_cap) return kLgCap;
+    int kept = 0, bad = 0;
+    for (int e = 0; e < E; ++e) {
+        const int off = et[2 * e];
+        const int cap = (e + 1 < E ? et[2 * e + 2] : total) - off;
+        const CfPose a = p.pose(e);
+        int n = 0;
+        const int r = __builtin_amdgcn_readfirstlane(
+            line_edge_wave(a.x, a.y, a.yaw, pyw + 4 * (size_t)e, sc.turn_radius, sc.step_size,
+                           px + off, py + off, cap, lane, &n));
+        // (the kept count is lane 0's: line_edge_wave's trim state lives in the lanes that wrote)
+        n = __builtin_amdgcn_readfirstlane(n);
+        if (r != kSteerSome) {
+            bad |= r == kSteerNone ? 2 : 4;
+            n = 0;
+        }
+        if (lane == 0) et[2 * e + 1] = n;
+        kept += n;
+    }
+    __syncthreads();
+    if (bad) return (bad & 2) ? kLgNone : kLgOverflow;
+    return kept;
+}
+
+template <class P, bool kWrite>
+__global__ __launch_bounds__(kCfLineThreads) void paths_kernel(SceneDev sc, PathsArgs a,
+                                                               CfLineBufs lb,
+                                                               int* __restrict__ err,
+                                                               const int* __restrict__ items,
+                                                               int items_cap) {
+    __shared__ int s_pos[kCfLevels];
+    const int tid = threadIdx.x;
+    const int pts_cap = lb.pts_cap;
+    double* px = lb.pts + (size_t)blockIdx.x * 3 * pts_cap;
+    double* py = px + pts_cap;
+    double* pyw = py + pts_cap;
+    int* et = lb.etab + (size_t)blockIdx.x * 2 * (lb.path_cap + kCfLevels + 1);
+    int* path = lb.path + (size_t)blockIdx.x * lb.path_cap;
+    // (a spill list counts the lines it had no room for, too)
+    const int n_items = min(items[0], items_cap);
+    for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+        const int* o = items + 1 + (size_t)it * kCfItem;
+        const int b = o[0];
+        __syncthreads();  // the buffers and s_pos served the previous item
+        if (tid < kCfLevels) s_pos[tid] = o[4 + tid];
+        const int q = a.qidx[b];
+        TreeDev tr = a.tr;
+        const size_t ro = (size_t)q * a.row_cap;
+        tr.x += ro;
+        tr.y += ro;
+        tr.yaw += ro;
+        tr.parent += ro;
+        const int D = cf_path(tr, a.nodes[b], path, lb.path_cap);
+        __syncthreads();
+        if (D < 0) {  // deeper than the tier's path capacity
+            if (lb.spill) cf_spill(lb, o, tid, err);
+            else if (tid == 0) atomicOr(err, 1);
+            continue;
+        }
+        const P p(tr, path, D, o, s_pos, a.goals + 3 * (size_t)q);
+        const int E = p.edges();
+        const int r = line_gen(sc, p, E, px, py, pyw, et, pts_cap, tid);
+        if (r == kLgCap) {
+            if (lb.spill) cf_spill(lb, o, tid, err);
+            else if (tid == 0) atomicOr(err, 8);
+            continue;
+        }
+        if (r == kLgNoneGoal && P::kGoalNoneOk) {
+            if (!kWrite && tid == 0) {
+                a.cnt[b] = 0;
+                a.okf[b] = 0;
+            }
+            continue;
+        }
+        if (r < 0) {
+            if (tid == 0) atomicOr(err, r == kLgOverflow ? 4 : 2);
+            continue;
+        }
+        const int npts = r + (P::kRootPoint ? 1 : 0);
+        if (!kWrite) {
+            if (tid == 0) {
+                a.cnt[b] = npts;
+                if (a.okf) a.okf[b] = 1;
+            }
+            continue;
+        }
+        // the packed row: the count pass and the scan sized it; anything else is a bug, never a
+        // store outside the row
+        const int64_t base = a.off[q];
+        if (a.off[q + 1] - base != (int64_t)npts) {
+            if (tid == 0) atomicOr(err, 16);
+            continue;
+        }
+        double* __restrict__ rx = a.ox + base;
+        double* __restrict__ ry = a.oy + base;
+        int cbase = 0;  // the edge's compact forward base
+        for (int e = 0; e < E; ++e) {
+            const int off = et[2 * e], n = et[2 * e + 1];
+            for (int i = tid; i < n; i += kCfLineThreads) {
+                const int w = npts - 1 - (cbase + i);
+                rx[w] = px[off + i];
+                ry[w] = py[off + i];
+            }
+            cbase += n;
+        }
+        if (P::kRootPoint && tid == 0) {
+            rx[0] = tr.x[path[0]];
+            ry[0] = tr.y[path[0]];
+        }
+        if (a.len) {
+            // euclidean_length of the row in line order: 64 hypots a round, added in lane order
+            __threadfence();
+            __syncthreads();
+            const volatile double* vx = rx;
+            const volatile double* vy = ry;
+            double len = 0.0;
+            for (int k0 = 0; k0 < npts - 1; k0 += 64) {
+                const int k = k0 + tid;
+                const double h = k < npts - 1 ? hypot(vx[k + 1] - vx[k], vy[k + 1] - vy[k]) : 0.0;
+                const int m = min(64, npts - 1 - k0);
+                for (int j = 0; j < m; ++j) len += readlane_f64(h, j);
+            }
+            if (tid == 0) a.len[b] = len;
+        }
+    }
+}
+
+// The packed rows' offsets: off[q] = the exclusive scan of the queries' point counts (slot[q]: the
+// query's item or -1; an item counts when okf says so), off[Q] the total; okq[q] the flag.  One
+// workgroup, 1024 queries a round.
+__global__ __launch_bounds__(1024) void paths_scan_kernel(int Q, const int* __restrict__ slot,
+                                                          const int* __restrict__ okf,
+                                                          const int* __restrict__ cnt,
+                                                          int64_t* __restrict__ off,
+                                                          uint8_t* __restrict__ okq) {
+    __shared__ int s_w[16];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (int q0 = 0; q0 < Q; q0 += 1024) {
+        const int q = q0 + tid;
+        int c = 0;
+        if (q < Q) {
+            const int b = slot[q];
+            const bool ok = b >= 0 && okf[b] != 0;
+            c = ok ? cnt[b] : 0;
+            okq[q] = ok ? 1 : 0;
+        }
+        const int incl = wave_incl_scan(c);
+        if (lane == 63) s_w[wave] = incl;
+        __syncthreads();
+        int wbase = 0;
+        for (int w = 0; w < wave; ++w) wbase += s_w[w];
+        const long long carry = s_carry;
+        if (q < Q) off[q] = carry + wbase + incl - c;
+        __syncthreads();
+        if (tid == 1023) s_carry = carry + wbase + incl;
+        __syncthreads();
+    }
+    if (tid == 0) off[Q] = s_carry;
+}
+
+template <class P, bool kWrite>
+static hipError_t launch_paths_t(hipStream_t st, const SceneDev& sc, const PathsArgs& a,
+                                 const CfLines& lines, int* err, const int* items, int k) {
+    if (lines.grid1 <= 0) return hipSuccess;
+    paths_kernel<P, kWrite><<<lines.grid1, kCfLineThreads, 0, st>>>(sc, a, lines.t1, err, items,
+                                                                    k);
+    if (lines.t1.spill)  // the lines past tier 1's capacities, at the full ones
+        paths_kernel<P, kWrite><<<lines.grid2, kCfLineThreads, 0, st>>>(
+            sc, a, lines.t2, err, lines.t1.spill, lines.t1.spill_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_paths(hipStream_t st, const SceneDev& sc, const PathsArgs& a,
+                        const CfLines& lines, int* err, const int* items, int k, bool star,
+                        bool write) {
+    if (!star) return launch_paths_t<CfChainPoses, true>(st, sc, a, lines, err, items, k);
+    return write ? launch_paths_t<StarChainPoses, true>(st, sc, a, lines, err, items, k)
+                 : launch_paths_t<StarChainPoses, false>(st, sc, a, lines, err, items, k);
+}
+
+hipError_t launch_paths_scan(hipStream_t st, int Q, const int* slot, const int* okf,
+                             const int* cnt, int64_t* off, uint8_t* okq) {
+    paths_scan_kernel<<<1, 1024, 0, st>>>(Q, slot, okf, cnt, off, okq);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------ RRT::plan of a query batch
 //
 // pp_batch_plan: check_finish (rrt.rs:428-438) of every accepted node of every query — nodes

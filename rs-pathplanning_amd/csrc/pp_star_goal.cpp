@@ -1,6 +1,7 @@
 // pp_star_goal.cpp — the RRT* batch's goal connection: the cheapest feasible goal edge of every
 // query (pp_star_plan), the un-pruned totals of one query (pp_star_goal_costs) and the path along
-// the rewired tree (pp_star_path).  DESIGN.md §3.7 "Goal connection".
+// the rewired tree (pp_star_path; every query's at once, on the device: pp_star_paths).  DESIGN.md
+// §3.7 "Goal connection".
 #include "pp_ctx.h"
 
 using namespace ppamd;
@@ -209,6 +210,76 @@ int pp_star_path(pp_ctx* ctx, int query, const double goal[3], int32_t node, dou
         std::memcpy(x, lx.data(), (size_t)w * sizeof(double));
         std::memcpy(y, ly.data(), (size_t)w * sizeof(double));
     }
+    return PP_OK;
+}
+
+int pp_star_paths(pp_ctx* ctx, const double* goals, const int32_t* nodes, int64_t* off, double* x,
+                  double* y, int64_t cap, int64_t* n_total, double* length, uint8_t* ok) {
+    int r = star_ready(ctx);
+    if (r) return r;
+    StarBatch& s = ctx->star;
+    if (!goals || !nodes || !off || !n_total)
+        return set_err(PP_ERR_INVALID_ARGUMENT, "null goals, nodes, off or n_total");
+    const int Q = s.f.Q;
+    for (int q = 0; q < Q; ++q)
+        if (!finite3(goals + 3 * (size_t)q)) return set_err(PP_ERR_INVALID_ARGUMENT, "non-finite goal");
+    hipStream_t st = ctx->stream;
+    PathExport& pe = ctx->paths;
+    int k = 0;
+    if ((r = paths_items(ctx, s.f, nodes, &k))) return r;
+    *n_total = 0;
+    if (length) std::fill(length, length + Q, 0.0);
+    if (k == 0) {
+        std::fill(off, off + Q + 1, (int64_t)0);
+        if (ok) std::fill(ok, ok + Q, (uint8_t)0);
+        return PP_OK;
+    }
+    // the line items (cf_line_kernel's layout): item b of the call, no optimize chain
+    std::vector<int> items(1 + (size_t)k * kCfItem, 0);
+    items[0] = k;
+    for (int b = 0; b < k; ++b) items[1 + (size_t)b * kCfItem] = b;
+    PP_HIP(pe.items.reserve(items.size()));
+    PP_HIP(s.goal_d.reserve(3 * (size_t)Q));
+    PP_HIP(hipMemcpyAsync(pe.items.p, items.data(), items.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemcpyAsync(s.goal_d.p, goals, 3 * (size_t)Q * sizeof(double), hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemsetAsync(pe.cnt.p, 0, (size_t)k * sizeof(int), st));
+    PP_HIP(hipMemsetAsync(pe.ok.p, 0, (size_t)k * sizeof(int), st));
+    PP_HIP(ctx->cf.err.reserve(2));
+    PP_HIP(hipMemsetAsync(ctx->cf.err.p, 0, 2 * sizeof(int), st));
+    const SceneDev sd = ctx->scene.dev(s.f.step, false);
+    PathsArgs a;
+    a.tr = s.f.tree_dev();
+    a.row_cap = s.f.cap;
+    a.qidx = pe.qidx.p;
+    a.nodes = pe.nodes.p;
+    a.goals = s.goal_d.p;
+    a.cnt = pe.cnt.p;
+    a.okf = pe.ok.p;
+    CfLines lines;
+    // the count pass: every item's points (and whether its goal edge has a word)
+    if ((r = paths_line_buffers(ctx, k, lines))) return r;
+    PP_HIP(launch_paths(st, sd, a, lines, ctx->cf.err.p, pe.items.p, k, true, false));
+    int err = 0;
+    PP_HIP(hipMemcpyAsync(&err, ctx->cf.err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    bool go = false;
+    r = paths_sizes(ctx, Q, off, x, y, cap, n_total, ok, &go);  // (synchronises: err is read)
+    if (err & 2) return set_err(PP_ERR_REFERENCE_PANIC, "a tree edge of a chain has no Dubins word");
+    if (err & 4) return set_err(PP_ERR_STEER_OVERFLOW, "generate_local_course would index past n_point");
+    if (err & 1) return set_err(PP_ERR_CAPACITY, "tree deeper than the path capacity");
+    if (err & 8) return set_err(PP_ERR_CAPACITY, "a line longer than the point capacity");
+    if (r || !go) return r;
+    // the write pass (the spill count zeroed again), with the rows' lengths
+    if ((r = paths_line_buffers(ctx, k, lines))) return r;
+    std::vector<double> hl(length ? (size_t)k : 0);
+    if (length) {
+        a.len = pe.len.p;
+        PP_HIP(hipMemsetAsync(pe.len.p, 0, (size_t)k * sizeof(double), st));
+    }
+    if ((r = paths_write(ctx, sd, a, lines, pe.items.p, k, true, x, y, *n_total,
+                         length ? hl.data() : nullptr)))
+        return r;
+    for (int q = 0, b = 0; length && q < Q; ++q)
+        if (nodes[q] >= 0) length[q] = hl[(size_t)b++];  // (items are the chosen nodes in query order)
     return PP_OK;
 }
 

@@ -45,9 +45,9 @@ EXPORTED = [
     "pp_rrt_iteration", "pp_rrt_tree_export", "pp_rrt_get_nearest_node_batch",
     "pp_rrt_verify_node_batch", "pp_rrt_check_finish_batch", "pp_rrt_check_finish",
     "pp_rrt_plan", "pp_batch_new", "pp_batch_set_window", "pp_batch_set_finish_schedule", "pp_batch_extend", "pp_batch_state", "pp_batch_tree_export",
-    "pp_batch_plan",
+    "pp_batch_plan", "pp_batch_paths",
     "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export",
-    "pp_star_plan", "pp_star_goal_costs", "pp_star_path",
+    "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
 ]
 
@@ -168,6 +168,8 @@ def lib():
             "pp_batch_state": ([vp, ip, i64p, i64p], C.c_int),
             "pp_batch_tree_export": ([vp, C.c_int, dp, dp, dp, ip, C.c_int64, i64p], C.c_int),
             "pp_batch_plan": ([vp, ip, dp, ip, ip, i64p], C.c_int),
+            "pp_batch_paths": ([vp, ip, i64p, dp, dp, C.c_int64, i64p, C.POINTER(C.c_uint8)],
+                               C.c_int),
             "pp_star_new": ([vp, C.c_int, dp, C.POINTER(C.c_uint64), C.c_int64, C.c_double,
                              C.c_int, C.c_double], C.c_int),
             "pp_star_extend": ([vp, C.c_int64, i64p, i64p, i64p], C.c_int),
@@ -176,6 +178,8 @@ def lib():
             "pp_star_plan": ([vp, dp, ip, dp, i64p], C.c_int),
             "pp_star_goal_costs": ([vp, C.c_int, dp, dp, C.c_int64, i64p], C.c_int),
             "pp_star_path": ([vp, C.c_int, dp, C.c_int32, dp, dp, C.c_int64, i64p, dp], C.c_int),
+            "pp_star_paths": ([vp, dp, ip, i64p, dp, dp, C.c_int64, i64p, dp,
+                               C.POINTER(C.c_uint8)], C.c_int),
             "pp_rrt_get_stats": ([vp, C.POINTER(StatsC), C.c_uint64], C.c_int),
             "pp_rrt_reset_stats": ([vp], C.c_int),
             "pp_set_profiling": ([vp, C.c_int], C.c_int),

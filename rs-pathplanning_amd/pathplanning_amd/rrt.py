@@ -533,6 +533,38 @@ class RRTBatch:
         return {"best_node": bn, "length": ln, "n_points": npts, "n_finishes": nf,
                 "checked": chk.value}
 
+    def paths(self, nodes=None):
+        """The finalized lines of every query in one call (pp_batch_paths): row q is the line
+        ``RRT.check_finish(nodes[q])`` returns on query q's tree with its goal, root side first.
+        ``nodes``: one node per query (-1: skip), or None: the best nodes of a ``plan()`` run
+        here (kept in ``self.last_plan``).  Returns (off int64[q + 1], xy float64[n, 2],
+        ok bool[q]): row q = ``xy[off[q]:off[q + 1]]``, empty where ``ok[q]`` is False."""
+        L = _ffi.lib()
+        ip, dp, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        u8 = C.POINTER(C.c_uint8)
+        off = np.zeros(self.q + 1, dtype=np.int64)
+        ok = np.zeros(self.q, dtype=np.uint8)
+        tot = C.c_int64(0)
+        if nodes is None:
+            # the plan's n_points are the rows' sizes: one call
+            self.last_plan = self.plan()
+            nodes = self.last_plan["best_node"]
+            cap = int(self.last_plan["n_points"].sum(dtype=np.int64))
+        else:
+            nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+            _ffi.check(L.pp_batch_paths(self.ctx.handle, nodes.ctypes.data_as(ip),
+                                        off.ctypes.data_as(i64), None, None, 0, C.byref(tot),
+                                        ok.ctypes.data_as(u8)))
+            cap = tot.value
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        x, y = np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+        if cap > 0:
+            _ffi.check(L.pp_batch_paths(self.ctx.handle, nodes.ctypes.data_as(ip),
+                                        off.ctypes.data_as(i64), x.ctypes.data_as(dp),
+                                        y.ctypes.data_as(dp), cap, C.byref(tot),
+                                        ok.ctypes.data_as(u8)))
+        return off, np.stack([x[:tot.value], y[:tot.value]], axis=1), ok.astype(bool)
+
     def tree(self, query: int, n: int | None = None):
         """(x, y, yaw, parent) of one query's tree, root first (``n``: its size, when known)."""
         n = int(self.state()[0][query]) if n is None else int(n)
@@ -659,6 +691,40 @@ class RRTStarBatch:
                                   x.ctypes.data_as(dp), y.ctypes.data_as(dp), n.value, C.byref(n),
                                   C.byref(length)))
         return np.stack([x, y], axis=1), length.value
+
+    def paths(self, goals, nodes=None):
+        """``path(q, goals[q], nodes[q])`` of every query in one call (pp_star_paths), generated
+        on the device.  ``goals``: a pose per query (one pose is broadcast); ``nodes``: one node
+        per query (-1: skip), or None: ``plan(goals)``'s best nodes.  The goal edge is not
+        verified again: any node's line is returned.  Returns (off int64[q + 1], xy
+        float64[n, 2], length float64[q], ok bool[q]): row q = ``xy[off[q]:off[q + 1]]``, root
+        first; empty with ``ok[q]`` False and length 0 where the node is -1 or its goal edge has
+        no Dubins word."""
+        g = np.asarray(goals, dtype=np.float64)
+        g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
+        g = np.ascontiguousarray(g, dtype=np.float64).reshape(self.q, 3)
+        if nodes is None:
+            nodes = self.plan(g)[0]
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+        L = _ffi.lib()
+        ip, dp, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        u8 = C.POINTER(C.c_uint8)
+        off = np.zeros(self.q + 1, dtype=np.int64)
+        ok = np.zeros(self.q, dtype=np.uint8)
+        length = np.zeros(self.q)
+        tot = C.c_int64(0)
+        _ffi.check(L.pp_star_paths(self.ctx.handle, g.ctypes.data_as(dp), nodes.ctypes.data_as(ip),
+                                   off.ctypes.data_as(i64), None, None, 0, C.byref(tot), None,
+                                   ok.ctypes.data_as(u8)))
+        cap = tot.value
+        x, y = np.zeros(max(cap, 1)), np.zeros(max(cap, 1))
+        if cap > 0:
+            _ffi.check(L.pp_star_paths(self.ctx.handle, g.ctypes.data_as(dp),
+                                       nodes.ctypes.data_as(ip), off.ctypes.data_as(i64),
+                                       x.ctypes.data_as(dp), y.ctypes.data_as(dp), cap,
+                                       C.byref(tot), length.ctypes.data_as(dp),
+                                       ok.ctypes.data_as(u8)))
+        return off, np.stack([x[:cap], y[:cap]], axis=1), length, ok.astype(bool)
 
     def close(self):
         self.ctx.close()
