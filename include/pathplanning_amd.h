@@ -34,7 +34,9 @@ extern "C" {
  * 5: pp_rrt_extend_samples and pp_rrt_tree_import (the host owns the RNG and the tree); nothing
  *    else changed
  * 5 (+): pp_star_plan / pp_star_goal_costs / pp_star_path added, nothing else changed
- * 5 (+): pp_batch_paths / pp_star_paths added, nothing else changed */
+ * 5 (+): pp_batch_paths / pp_star_paths added, nothing else changed
+ * 5 (+): pp_rrt_revalidate / pp_batch_revalidate added (a tree kept across a scene change),
+ *    nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -238,6 +240,23 @@ int pp_rrt_get_nearest_node_batch(pp_ctx* ctx, const double* qx, const double* q
 int pp_rrt_verify_node_batch(pp_ctx* ctx, const double* x, const double* y,
                              const int32_t* parent, int k, uint8_t* ok, double* yaw);
 
+/* Re-verify the planner's tree against the context's current Space and drop every node whose
+ * line_to_origin no longer verifies (RRT::verify_node, rrt.rs:414-426, per node): node i > 0 stays
+ * when Space::verify accepts the Dubins points from its stored pose to its parent's stored pose
+ * followed by the parent's point (the stored yaw is used, rrt.rs:301-311; a None steer gives the
+ * two-point line) and its parent stays.  The root always stays (RRT::new inserts it unverified,
+ * rrt.rs:344-346); a root the new scene covers takes every other node with it.  Kept nodes keep
+ * their order and their poses bit for bit, parents are remapped.  Accepted on a valid planner and
+ * on one that a later pp_space_new, pp_space_new_polygons or pp_space_set_grid invalidated while
+ * its tree is still on the device (every other call on such a planner stays PP_ERR_STATE, and
+ * pp_rrt_new starts from a root as before); on success the planner is valid for the new scene
+ * and later extends, plans and queries continue on the pruned tree.  The iteration counter, seed,
+ * goal, step size, window and statistics stay; what pp_rrt_new derives from the scene is derived
+ * again.  *n_kept (may be NULL) = the nodes that stay; new_index (may be NULL): one entry per node
+ * before the call, its index afterwards or -1 when dropped.  PP_ERR_STATE without a tree;
+ * PP_ERR_STEER_OVERFLOW leaves the tree unmodified.  RRT* batches are not covered. */
+int pp_rrt_revalidate(pp_ctx* ctx, int64_t* n_kept, int32_t* new_index);
+
 /* --------------------------------------------------- goal connection (src/rrt.rs:428-619) */
 /* RRT::check_finish (rrt.rs:428-438) for k tree nodes: optimize_from_goal's shortcut search
  * (rrt.rs:463-501, RECURSION_LIMIT 16), finalize's line (rrt.rs:503-540) and its verify.
@@ -320,6 +339,14 @@ int pp_batch_plan(pp_ctx* ctx, int32_t* best_node, double* length, int32_t* n_po
  * are not modified. */
 int pp_batch_paths(pp_ctx* ctx, const int32_t* nodes, int64_t* off, double* x, double* y,
                    int64_t cap, int64_t* n_total, uint8_t* ok);
+/* pp_rrt_revalidate for every query's tree of the batch, against the context's current Space; a
+ * batch that a later pp_space_new or pp_space_new_polygons invalidated is accepted and valid again
+ * afterwards.  The iteration counters, seeds, goals, step size, window and statistics stay.
+ * n_nodes (q, may be NULL): the tree sizes after the call; *n_dropped (may be NULL): the nodes
+ * dropped over the batch; new_index (may be NULL): the sum of the old tree sizes, query i's
+ * entries at the prefix sum of pp_batch_state's n_nodes read before the call, each a node's index
+ * in its tree afterwards or -1.  PP_ERR_STATE without a batch. */
+int pp_batch_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_t* new_index);
 /* one query's tree (root first), like pp_rrt_tree_export */
 int pp_batch_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* yaw,
                          int32_t* parent, int64_t cap, int64_t* n);

@@ -402,6 +402,7 @@ int pp_batch_new(pp_ctx* ctx, int q, const double* starts, const double* goals,
     if ((int64_t)q * (max_iter + 1) > ((int64_t)1 << 34)) return set_err(PP_ERR_CAPACITY, "batch too large");
     Batch& b = ctx->batch;
     b.valid = false;
+    b.stale = false;
     hipStream_t st = ctx->stream;
     PP_HIP(b.itprev.reserve(q));
     PP_HIP(b.state.reserve(1 + kMaxSub));

@@ -7,6 +7,7 @@
 //   pp_batch.cpp    the forest of per-query trees, pp_batch_*, pp_star_*
 //   pp_star_goal.cpp  the RRT* goal connection: pp_star_plan, pp_star_goal_costs, pp_star_path,
 //                     pp_star_paths
+//   pp_revalidate.cpp  a tree across a scene change: pp_rrt_revalidate, pp_batch_revalidate
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -178,6 +179,7 @@ struct Scene {
 // ---- planner (RRT): the one tree and its window buffers
 struct Planner {
     bool valid = false;  // pp_rrt_new succeeded for the current scene
+    bool stale = false;  // a scene change invalidated the planner, its tree is still on the device
     double start[3] = {0, 0, 0}, goal[3] = {0, 0, 0};
     int64_t max_iter = 0;
     double step = 0.1;
@@ -343,6 +345,7 @@ struct Forest {
 // pp_batch_plan's buffers
 struct Batch {
     bool valid = false;  // false on entry to pp_batch_new, true only on its success
+    bool stale = false;  // a scene change invalidated the batch, its forest is still on the device
     Forest f;
     DBuf<double> yawbuf;
     DBuf<int> status, err, alist, lstat;
@@ -398,6 +401,20 @@ struct StarBatch {
     DBuf<long long> gsteer;
 };
 
+// ---- revalidation (pp_rrt_revalidate / pp_batch_revalidate: RevalArgs), reserved on first use
+constexpr int kRevalSlice = 32768;  // steer tasks per slice
+struct Reval {
+    DBuf<SteerTask> tasks;
+    DBuf<StarTaskExt> ext;
+    DBuf<PrepRec> rec;
+    DBuf<int> status, off, bsum, pos, new_index, spar, err;
+    DBuf<double> yaw, sx, sy, syaw;
+    DBuf<long long> srow;
+    DBuf<unsigned> v0, v1;
+    DBuf<uint8_t> blocked;
+    DBuf<DevState> state;
+};
+
 // ---- profiling
 struct Profiling {
     bool on = false;
@@ -444,6 +461,7 @@ struct pp_ctx {
     ppamd::Batch batch;
     ppamd::StarBatch star;
     ppamd::PathExport paths;
+    ppamd::Reval reval;
     ppamd::Profiling prof;
 
     // the scene as the one-tree planner's kernels see it (its step, its blocked root)

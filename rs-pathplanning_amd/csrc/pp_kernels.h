@@ -290,6 +290,43 @@ struct StarGoalArgs {
 };
 hipError_t launch_star_goal(hipStream_t s, const StarGoalArgs& g, int rounds);
 
+// Revalidation (pp_rrt_revalidate / pp_batch_revalidate, pp_k_revalidate.hip): re-verify every
+// node's edge against the scene, propagate failures to the descendants and compact the trees in
+// place.  `total` nodes in Q trees: tree q's nodes are g = off[q] .. off[q + 1] - 1, node i of it
+// in row q * cap + i of tr (x32 / y32 null: a forest without screen copies).
+struct RevalArgs {
+    TreeDev tr{};
+    int Q = 1;
+    size_t cap = 0;
+    const int* off = nullptr;          // [Q + 1] exclusive scan of the trees' node counts
+    int total = 0;                     // off[Q]
+    const uint8_t* blocked = nullptr;  // [Q] the root fails verify (polygon mode; may be null)
+    int* n = nullptr;                  // [Q] the trees' node counts, rewritten (may be null)
+    // one slice of steer tasks at a time
+    int slice = 0;
+    SteerTask* tasks = nullptr;
+    StarTaskExt* ext = nullptr;
+    PrepRec* rec = nullptr;
+    int* status = nullptr;
+    double* yaw = nullptr;
+    DevState* st = nullptr;
+    unsigned* v[2] = {nullptr, nullptr};  // [total] ping-pong: ancestor | bad << 31
+    int* bsum = nullptr;       // [ceil(total / 1024)] scan workgroup counts
+    int* pos = nullptr;        // [total + 1] exclusive scan of keep; pos[total]: the kept nodes
+    int* new_index = nullptr;  // [total] index in its tree after the call, -1 dropped
+    double* sx = nullptr;      // [total] and below: the kept rows, staged compactly
+    double* sy = nullptr;
+    double* syaw = nullptr;
+    int* spar = nullptr;
+    long long* srow = nullptr;  // ... and the row each goes back to
+    int* err = nullptr;         // != 0: a steer overflowed n_point; the trees are left as they are
+    double* lit_scratch = nullptr;  // kLiteralWaves buffers
+    int* lit_locks = nullptr;
+    long long* wg_points = nullptr;  // profiling: walked points per walk workgroup (or null)
+};
+// passes: ceil(log2(the largest tree's node count)) pointer-doubling passes
+hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs& a, int passes);
+
 // dubins_path_planning_from_origin for n (dx, dy, eyaw, c, step_size) configurations
 hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int cap, double* px,
                                 double* py, double* pyaw, int* n_out, int* word_out,

@@ -123,6 +123,7 @@ int pp_rrt_new(pp_ctx* ctx, double sx, double sy, double syaw, double gx, double
     if (!(step_size > 0.0) || max_iter < 0)
         return set_err(PP_ERR_INVALID_ARGUMENT, "step_size must be > 0 and max_iter >= 0");
     ctx->rrt.valid = false;
+    ctx->rrt.stale = false;
     PP_HIP(hipStreamSynchronize(ctx->stream));
     ctx->rrt.n = 0;
     ctx->rrt.it = 0;

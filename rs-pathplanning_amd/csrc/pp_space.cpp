@@ -74,6 +74,9 @@ void install_scene(pp_ctx* ctx, double minx, double maxx, double miny, double ma
     s.m = m;
     s.has_grid = false;
     s.valid = true;
+    // the trees stay on the device: pp_rrt_revalidate / pp_batch_revalidate carry them over
+    ctx->rrt.stale |= ctx->rrt.valid;
+    ctx->batch.stale |= ctx->batch.valid;
     ctx->rrt.valid = false;
     ctx->batch.valid = false;
 }
@@ -198,6 +201,7 @@ int pp_space_set_grid(pp_ctx* ctx, const uint32_t* bits, int w, int h, double x0
         PP_HIP(hipMemcpy(s.d_gimg.p, img.data(), img_bytes, hipMemcpyHostToDevice));
     }
     s.has_grid = true;
+    ctx->rrt.stale |= ctx->rrt.valid;
     ctx->rrt.valid = false;  // the planner's Space changed (rrt.rs:342)
     return PP_OK;
 }

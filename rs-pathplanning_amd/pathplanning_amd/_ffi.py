@@ -46,6 +46,7 @@ EXPORTED = [
     "pp_rrt_verify_node_batch", "pp_rrt_check_finish_batch", "pp_rrt_check_finish",
     "pp_rrt_plan", "pp_batch_new", "pp_batch_set_window", "pp_batch_set_finish_schedule", "pp_batch_extend", "pp_batch_state", "pp_batch_tree_export",
     "pp_batch_plan", "pp_batch_paths",
+    "pp_rrt_revalidate", "pp_batch_revalidate",
     "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
@@ -170,6 +171,8 @@ def lib():
             "pp_batch_plan": ([vp, ip, dp, ip, ip, i64p], C.c_int),
             "pp_batch_paths": ([vp, ip, i64p, dp, dp, C.c_int64, i64p, C.POINTER(C.c_uint8)],
                                C.c_int),
+            "pp_rrt_revalidate": ([vp, i64p, ip], C.c_int),
+            "pp_batch_revalidate": ([vp, ip, i64p, ip], C.c_int),
             "pp_star_new": ([vp, C.c_int, dp, C.POINTER(C.c_uint64), C.c_int64, C.c_double,
                              C.c_int, C.c_double], C.c_int),
             "pp_star_extend": ([vp, C.c_int64, i64p, i64p, i64p], C.c_int),

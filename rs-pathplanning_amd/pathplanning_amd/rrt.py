@@ -263,6 +263,27 @@ class RRT:  # rrt.rs:325-620
             self.ctx.handle, x.ctypes.data_as(dp), y.ctypes.data_as(dp), yaw.ctypes.data_as(dp),
             parent.ctypes.data_as(C.POINTER(C.c_int32)), len(x)))
 
+    def revalidate(self, n_old: int | None = None):
+        """Re-verify the tree against the context's current scene and drop every node whose
+        line_to_origin no longer verifies (pp_rrt_revalidate; the root stays, kept nodes keep
+        their order and poses).  Returns (n_kept, new_index int32[old n]): a node's index
+        afterwards, -1 when dropped.  ``n_old``: the tree's size, for a planner whose scene was
+        replaced behind its back (``tree_size`` refuses then)."""
+        n_old = self.tree_size() if n_old is None else int(n_old)
+        new_index = np.zeros(max(n_old, 1), dtype=np.int32)
+        kept = C.c_int64(0)
+        _ffi.check(_ffi.lib().pp_rrt_revalidate(
+            self.ctx.handle, C.byref(kept), new_index.ctypes.data_as(C.POINTER(C.c_int32))))
+        return kept.value, new_index[:n_old]
+
+    def set_space(self, space: Space):
+        """Replace the scene and keep the tree where it still verifies: uploads ``space`` into
+        the planner's context and revalidates.  Returns (n_kept, new_index) as ``revalidate``."""
+        n_old = self.tree_size()
+        space._upload(self.ctx)
+        self.space = space
+        return self.revalidate(n_old)
+
     def plan_one(self) -> bool:
         """plan_one's extend (rrt.rs:583-589): True when the node was inserted."""
         acc = C.c_int32(0)
@@ -515,6 +536,29 @@ class RRTBatch:
 
     def set_profiling(self, on: bool):
         _ffi.check(_ffi.lib().pp_set_profiling(self.ctx.handle, int(bool(on))))
+
+    def revalidate(self, n_old=None):
+        """Re-verify every query's tree against the context's current scene (pp_batch_revalidate)
+        and drop the nodes whose line_to_origin no longer verifies.  Returns (n_nodes int32[q]
+        after the call, new_index int32[sum of the old sizes]): query q's entries start at the
+        prefix sum of the old sizes, each a node's index in its tree afterwards or -1.
+        ``n_old``: the old sizes, for a batch whose scene was replaced behind its back."""
+        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
+        new_index = np.zeros(max(int(n_old.sum(dtype=np.int64)), 1), dtype=np.int32)
+        n = np.zeros(self.q, dtype=np.int32)
+        dropped = C.c_int64(0)
+        ip = C.POINTER(C.c_int32)
+        _ffi.check(_ffi.lib().pp_batch_revalidate(
+            self.ctx.handle, n.ctypes.data_as(ip), C.byref(dropped), new_index.ctypes.data_as(ip)))
+        self.last_dropped = dropped.value
+        return n, new_index[:int(n_old.sum(dtype=np.int64))]
+
+    def set_space(self, space: Space):
+        """Replace the scene of the batch and keep every tree where it still verifies."""
+        n_old = self.state()[0]
+        space._upload(self.ctx)
+        self.space = space
+        return self.revalidate(n_old)
 
     def plan(self):
         """RRT::plan (rrt.rs:599-619) of every query on its tree as extended so far: check_finish

@@ -1,0 +1,364 @@
+"""A tree kept across a scene change: pp_rrt_revalidate / pp_batch_revalidate
+against the CPU restatement tests/revalidate_ref.py (per-edge verify with the stored yaw, the
+sequential keep loop, the stable compaction).  The tree is grown on the GPU, exported, and restated
+on the CPU from the exported poses.
+
+Exact: the kept set, new_index, coordinates, stored yaw, remapped parents.  Each case asserts its
+own conditions on the restatement (a prune that drops something, orphans, ...), so a scene that
+stops exercising the case fails the test instead of passing vacuously."""
+import numpy as np
+import pytest
+
+import revalidate_ref as ref
+from test_gpu_parity import _assert_same_tree, _planner
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx(pkg):
+    c = pkg.Context(0)
+    yield c
+    c.close()
+
+
+def _space(raw):
+    from pathplanning_amd import rrt
+
+    return rrt.Space.from_raw(raw)
+
+
+def _grown(pkg, raw, seed, n_iter, window=4096, ctx=None):
+    p = _planner(pkg, raw, seed, window, ctx)
+    p.extend(n_iter)
+    return p, p.tree()
+
+
+def _assert_exact(got, exp):
+    for a, b in zip(got, exp):
+        assert len(a) == len(b), (len(a), len(b))
+        assert np.array_equal(a, b)
+
+
+def _revalidate_checked(oracle_mod, p, before, raw_new):
+    """set_space(raw_new) on planner p holding `before`; the result against the restatement"""
+    r = ref.revalidate(oracle_mod.OracleScene.from_raw(raw_new), before)
+    kept, new_index = p.set_space(_space(raw_new))
+    assert kept == r["kept"] == p.tree_size(), (kept, r["kept"])
+    assert np.array_equal(new_index, r["new_index"]), np.flatnonzero(new_index != r["new_index"])[:10]
+    _assert_exact(p.tree(), r["tree"])
+    return r
+
+
+def _oracle_continue(oracle_mod, raw, tree, seed, it0, n_iter):
+    sc = oracle_mod.OracleScene.from_raw(raw)
+    tr = oracle_mod.OracleTree(raw["start"], len(tree[0]) + n_iter + 1)
+    n = len(tree[0])
+    tr.x[:n], tr.y[:n], tr.yaw[:n], tr.parent[:n] = tree
+    tr._c.n = n
+    oracle_mod.rrt_extend(sc, tr, seed, it0, n_iter)
+    return sc, tr
+
+
+def _disc_on_quarter_subtree(raw, tree, r=0.3):
+    x, y, _, par = tree
+    cnt = ref.descendants(par)
+    v = 1 + int(np.argmin(np.abs(cnt[1:] - len(x) / 4.0)))
+    return ref.with_discs(raw, [(x[v], y[v], r)])
+
+
+# ------------------------------------------------------------------ 1. the unchanged scene
+@pytest.mark.parametrize("scene,seed,n_iter", [("bench6", 7, 3000), ("field512", 9, 12000)])
+def test_unchanged_scene_is_the_identity(pkg, ctx, scene, seed, n_iter):
+    from pathplanning_amd import scenes
+
+    raw = getattr(scenes, scene)()
+    p, before = _grown(pkg, raw, seed, n_iter, ctx=ctx)
+    n = len(before[0])
+    for call in (p.revalidate, lambda: p.set_space(_space(raw))):
+        kept, new_index = call()
+        assert kept == n == p.tree_size() and p.iteration() == n_iter
+        assert np.array_equal(new_index, np.arange(n))
+        _assert_exact(p.tree(), before)
+
+
+@pytest.mark.parametrize("window", [7, 4096])
+@pytest.mark.parametrize("scene,seed,n1,n2", [("bench6", 7, 2000, 1000),
+                                              ("field512", 9, 9000, 3000)])
+def test_revalidate_between_extends_changes_nothing(pkg, ctx, scene, seed, n1, n2, window):
+    from pathplanning_amd import scenes
+
+    raw = getattr(scenes, scene)()
+    a, _ = _grown(pkg, raw, seed, n1 + n2, window, ctx)
+    whole = a.tree()
+    b, _ = _grown(pkg, raw, seed, n1, window, ctx)
+    b.revalidate()
+    b.extend(n2)
+    assert b.iteration() == n1 + n2
+    _assert_exact(b.tree(), whole)
+
+
+# ------------------------------------------------------- 2. + 7. one disc, and what follows
+def test_bench6_one_disc_then_continue(pkg, ctx, oracle_mod):
+    from pathplanning_amd import scenes
+
+    raw = scenes.bench6()
+    n1, n2 = 3000, 2000
+    p, before = _grown(pkg, raw, 7, n1, ctx=ctx)
+    raw2 = _disc_on_quarter_subtree(raw, before)
+    r = _revalidate_checked(oracle_mod, p, before, raw2)
+    assert 0 < r["kept"] < len(before[0]) and r["orphans"] > 0, r
+    assert p.iteration() == n1
+    # the extend continues on the pruned tree under the new scene, from the planner's counter
+    p.extend(n2)
+    sc2, tr = _oracle_continue(oracle_mod, raw2, r["tree"], 7, n1, n2)
+    _assert_same_tree(p.tree(), tr.arrays())
+    # check_finish of kept nodes on the pruned tree (the tree as it was right after the prune)
+    q, _ = _grown(pkg, scenes.bench6_open(), 7, n1, ctx=ctx)
+    qb = q.tree()
+    raw3 = _disc_on_quarter_subtree(scenes.bench6_open(), qb)
+    r3 = _revalidate_checked(oracle_mod, q, qb, raw3)
+    assert 50 < r3["kept"] < len(qb[0])
+    nodes = np.linspace(1, r3["kept"] - 1, 50).astype(np.int32)
+    got = q.check_finish_batch(nodes)
+    sc3, tr3 = _oracle_continue(oracle_mod, raw3, r3["tree"], 7, n1, 0)
+    exp = [oracle_mod.check_finish(sc3, tr3, int(v), raw3["goal"][:2], raw3["goal"][2]) for v in nodes]
+    assert np.array_equal(got["ok"], [e["ok"] for e in exp])
+    assert got["ok"].any()
+    for k, e in enumerate(exp):
+        if e["ok"]:
+            assert abs(got["length"][k] - e["length"]) <= 1e-9 * max(1.0, e["length"])
+
+
+# ------------------------------------- 3. field512: more than one slice and one scan tile
+@pytest.mark.parametrize("n_discs", [8, 32])
+def test_field512_prunes(pkg, ctx, oracle_mod, n_discs):
+    from pathplanning_amd import scenes
+
+    raw = scenes.field512()
+    n1 = 40000
+    p, before = _grown(pkg, raw, 9, n1, ctx=ctx)
+    assert len(before[0]) > 8192  # several 1024-node scan tiles, a depth of ~50
+    raw2 = ref.with_discs(raw, ref.extra_discs(raw, n_discs))
+    r = _revalidate_checked(oracle_mod, p, before, raw2)
+    assert r["orphans"] > 0 and 1 < r["kept"] < len(before[0]), r
+    p.extend(3000)
+    _, tr = _oracle_continue(oracle_mod, raw2, r["tree"], 9, n1, 3000)
+    _assert_same_tree(p.tree(), tr.arrays())
+
+
+def test_more_than_one_slice_of_steer_tasks(pkg, ctx, oracle_mod):
+    """the steer round takes the tree in slices of 32768 tasks, enqueued back to back"""
+    from pathplanning_amd import scenes
+
+    raw = scenes.field512()
+    p, before = _grown(pkg, raw, 9, 150000, ctx=ctx)
+    assert len(before[0]) > 32768 + 1024
+    raw2 = ref.with_discs(raw, ref.extra_discs(raw, 8))
+    r = _revalidate_checked(oracle_mod, p, before, raw2)
+    assert r["orphans"] > 0 and 1 < r["kept"] < len(before[0]), r
+    late = np.flatnonzero(~r["edge_ok"])
+    assert late.min() < 32768 < late.max()  # edges fail in both slices
+
+
+# ----------------------------------------------------------------------- 4. a covered root
+def test_root_covered_by_a_disc(pkg, ctx, oracle_mod):
+    from pathplanning_amd import scenes
+
+    raw = scenes.bench6()
+    p, before = _grown(pkg, raw, 7, 3000, ctx=ctx)
+    raw2 = ref.with_discs(raw, [(raw["start"][0], raw["start"][1], 0.2)])
+    r = _revalidate_checked(oracle_mod, p, before, raw2)
+    assert r["kept"] == 1 and len(before[0]) > 1000
+    assert np.array_equal(p.tree()[0], before[0][:1])
+
+
+def test_root_inside_a_polygon(pkg, ctx, oracle_mod):
+    """transit with the start moved into an obstacle (test_polygon_root_blocked's start): the tree
+    grows while that obstacle is absent, then the full scene comes back — only the root stays and
+    the planner is root-blocked"""
+    from pathplanning_amd import scenes
+
+    full = dict(scenes.transit())
+    c = full["obstacle_polygons"][2].mean(axis=0)
+    full["start"] = (float(c[0]), float(c[1]), 0.3)
+    grow = dict(full)
+    grow["obstacle_polygons"] = [o for k, o in enumerate(full["obstacle_polygons"]) if k != 2]
+    p, before = _grown(pkg, grow, 1, 3000, ctx=ctx)
+    assert len(before[0]) > 20
+    r = _revalidate_checked(oracle_mod, p, before, full)
+    assert r["kept"] == 1
+    assert p.extend(500) == 0 and p.tree_size() == 1 and p.iteration() == 3500
+    ok, _ = p.verify_node_batch([full["start"][0] + 0.05], [full["start"][1]], [0])
+    assert not ok[0]
+
+
+# ------------------------------------------------------------------ 5. the other scene modes
+def test_field512_tree_under_the_grid(pkg, ctx, oracle_mod):
+    from pathplanning_amd import scenes
+
+    p, before = _grown(pkg, scenes.field512(), 9, 12000, ctx=ctx)
+    r = _revalidate_checked(oracle_mod, p, before, scenes.field512_grid())
+    assert 1 < r["kept"] < len(before[0]), r
+    p.extend(2000)
+    _, tr = _oracle_continue(oracle_mod, scenes.field512_grid(), r["tree"], 9, 12000, 2000)
+    _assert_same_tree(p.tree(), tr.arrays())
+
+
+def test_bench6_tree_under_its_polygons(pkg, ctx, oracle_mod):
+    from pathplanning_amd import scenes
+
+    p, before = _grown(pkg, scenes.bench6(), 7, 3000, ctx=ctx)
+    r = _revalidate_checked(oracle_mod, p, before, scenes.bench6_polygons())
+    assert r["kept"] > 1
+    p.extend(1000)
+    _, tr = _oracle_continue(oracle_mod, scenes.bench6_polygons(), r["tree"], 7, 3000, 1000)
+    _assert_same_tree(p.tree(), tr.arrays())
+
+
+def test_transit_tree_with_an_added_ring(pkg, ctx, oracle_mod):
+    from pathplanning_amd import scenes
+
+    raw = scenes.transit()
+    p, before = _grown(pkg, raw, 1, 4000, ctx=ctx)
+    x, y, _, par = before
+    cnt = ref.descendants(par)
+    v = 1 + int(np.argmin(np.abs(cnt[1:] - len(x) / 4.0)))
+    raw2 = dict(raw)
+    sq = np.array([(-1.0, -1.0), (1.0, -1.0), (1.0, 1.0), (-1.0, 1.0)]) + (x[v], y[v])
+    raw2["obstacle_polygons"] = list(raw["obstacle_polygons"]) + [sq]
+    r = _revalidate_checked(oracle_mod, p, before, raw2)
+    assert 1 < r["kept"] < len(x) and r["orphans"] > 0, r
+
+
+# --------------------------------------------------------------------- 6. imported trees
+def test_imported_tree_duplicates_and_stored_yaws(pkg, ctx, oracle_mod):
+    """an imported tree carries any yaw and may hold a child on its parent (the literal path's
+    trim case): the stored yaw decides the edge, not compute_yaw"""
+    from pathplanning_amd import scenes
+
+    raw = scenes.bench6()
+    p, grown = _grown(pkg, raw, 7, 1500, ctx=ctx)
+    x, y, yaw, par = (a.copy() for a in grown)
+    n = len(x)
+    rng = np.random.default_rng(5)
+    # another yaw on half of the leaves and on a few inner nodes (their subtrees become orphans)
+    cnt = ref.descendants(par)
+    leaves, inner = np.flatnonzero(cnt == 0), np.flatnonzero((cnt > 0) & (cnt < 40))
+    turned = np.concatenate([rng.choice(leaves, len(leaves) // 2, replace=False),
+                             rng.choice(inner[inner > 0], 5, replace=False)])
+    yaw[turned] = rng.uniform(-7.0, 7.0, len(turned))
+    # children on their parents: the same pose, another yaw, and a grandchild on both
+    on = rng.choice(np.setdiff1d(np.arange(1, n), turned), 24, replace=False)
+    dx, dy = x[on], y[on]
+    dyaw = np.where(np.arange(24) % 2 == 0, yaw[on], rng.uniform(-3.0, 3.0, 24))
+    x, y, yaw = np.append(x, dx), np.append(y, dy), np.append(yaw, dyaw)
+    par = np.append(par, on).astype(np.int32)
+    x, y, yaw = np.append(x, dx[:8]), np.append(y, dy[:8]), np.append(yaw, dyaw[:8] + 0.5)
+    par = np.append(par, n + np.arange(8)).astype(np.int32)
+    tree = (x, y, yaw, par)
+    sc = oracle_mod.OracleScene.from_raw(raw)
+    r = ref.revalidate(sc, tree)
+    # under compute_yaw every grown edge verifies in its own scene: a drop is the stored yaw's doing
+    assert ref.revalidate(sc, grown)["kept"] == n
+    assert 1 < r["kept"] < len(x) and r["orphans"] > 0, r
+    p.tree_import(*tree)
+    kept, new_index = p.revalidate()
+    assert kept == r["kept"]
+    assert np.array_equal(new_index, r["new_index"]), np.flatnonzero(new_index != r["new_index"])[:10]
+    _assert_exact(p.tree(), r["tree"])
+
+
+# ------------------------------------------------------------------------------ 8. the batch
+def test_batch(pkg, oracle_mod):
+    from pathplanning_amd import rrt, scenes
+
+    raw = scenes.field512()
+    raw2 = ref.with_discs(raw, ref.extra_discs(raw, 8))
+    sc2 = oracle_mod.OracleScene.from_raw(raw2)
+    Q, n1, max_iter = 64, 600, 900
+    starts, goals, seeds = scenes.config3_queries(raw, 0, Q)
+    after = []
+    for window in (1, 32):
+        c = pkg.Context(0)
+        b = rrt.RRTBatch(starts, goals, max_iter, raw["step_size"], _space(raw), seeds, ctx=c,
+                         window=window)
+        b.extend(n1)
+        n_old, it_old = b.state()
+        before = [b.tree(q, n_old[q]) for q in range(Q)]
+        n_new, new_index = b.set_space(_space(raw2))
+        off = np.concatenate([[0], np.cumsum(n_old)])
+        assert len(new_index) == off[-1]
+        if window == 1:
+            exp = [ref.revalidate(sc2, t) for t in before]
+        for q in range(Q):
+            assert n_new[q] == exp[q]["kept"], q
+            assert np.array_equal(new_index[off[q]:off[q + 1]], exp[q]["new_index"]), q
+            _assert_exact(b.tree(q, n_new[q]), exp[q]["tree"])
+        dropped = [int(n_old[q] - n_new[q]) for q in range(Q)]
+        assert b.last_dropped == sum(dropped)
+        assert max(dropped) > 0 and min(dropped) == 0, dropped
+        assert sum(e["orphans"] for e in exp) > 0
+        assert np.array_equal(b.state()[1], it_old)
+        b.extend(max_iter)
+        n_end, it_end = b.state()
+        assert (it_end == max_iter).all()
+        after.append([b.tree(q, n_end[q]) for q in range(Q)])
+        if window == 32:
+            plan = b.plan()
+            off_p, xy, ok = b.paths(plan["best_node"])
+            assert np.array_equal(ok, plan["best_node"] >= 0)
+            lines = [xy[off_p[q]:off_p[q + 1]] for q in range(Q) if ok[q]]
+            assert all(sc2.verify_line(l[:, 0], l[:, 1]) for l in lines)
+        c.close()
+    for q in range(Q):
+        _assert_exact(after[0][q], after[1][q])
+    for q in (0, int(np.argmax(dropped)), Q - 1):  # ... and the oracle's run from the pruned tree
+        raw_q = dict(raw2)
+        raw_q["start"] = tuple(starts[q])
+        _, tr = _oracle_continue(oracle_mod, raw_q, exp[q]["tree"], int(seeds[q]), n1, max_iter - n1)
+        _assert_same_tree(after[0][q], tr.arrays())
+
+
+# ----------------------------------------------------------------------- 9. state errors
+def test_state_errors(pkg, oracle_mod):
+    import ctypes as C
+
+    from pathplanning_amd import _ffi, rrt, scenes
+
+    L = _ffi.lib()
+    raw = scenes.bench6()
+    c = pkg.Context(0)
+    assert L.pp_rrt_revalidate(c.handle, None, None) == _ffi.PP_ERR_STATE  # no scene
+    _space(raw)._upload(c)
+    assert L.pp_rrt_revalidate(c.handle, None, None) == _ffi.PP_ERR_STATE  # no planner
+    assert L.pp_batch_revalidate(c.handle, None, None, None) == _ffi.PP_ERR_STATE
+    p, before = _grown(pkg, raw, 7, 1500, ctx=c)
+    raw2 = _disc_on_quarter_subtree(raw, before)
+    _space(raw2)._upload(c)
+    # stale: every other call refuses, as before
+    acc, n = C.c_int64(0), C.c_int64(0)
+    assert L.pp_rrt_extend(c.handle, 10, C.byref(acc)) == _ffi.PP_ERR_STATE
+    assert L.pp_rrt_tree_size(c.handle, C.byref(n)) == _ffi.PP_ERR_STATE
+    kept, new_index = p.revalidate(len(before[0]))
+    r = ref.revalidate(oracle_mod.OracleScene.from_raw(raw2), before)
+    assert kept == r["kept"] and np.array_equal(new_index, r["new_index"])
+    assert p.tree_size() == kept and p.extend(100) >= 0
+    # a new planner after a scene change still starts from a root, and is not stale
+    _space(raw)._upload(c)
+    q = _planner(pkg, raw, 3, 256, c)
+    assert q.tree_size() == 1 and q.iteration() == 0
+    assert q.revalidate()[0] == 1
+    # the batch: stale after a scene change, valid again after the call
+    starts, goals, seeds = scenes.config3_queries(raw, 0, 4)
+    b = rrt.RRTBatch(starts, goals, 200, raw["step_size"], _space(raw), seeds, ctx=c)
+    b.extend(100)
+    n_old = b.state()[0]
+    _space(raw2)._upload(c)
+    it = C.c_int64(0)
+    assert L.pp_batch_extend(c.handle, 1, C.byref(it), None) == _ffi.PP_ERR_STATE
+    n_new, _ = b.revalidate(n_old)
+    assert (n_new <= n_old).all() and (n_new >= 1).all()
+    b.extend(100)
+    assert (b.state()[1] == 200).all()
+    c.close()
