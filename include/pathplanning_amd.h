@@ -36,7 +36,9 @@ extern "C" {
  * 5 (+): pp_star_plan / pp_star_goal_costs / pp_star_path added, nothing else changed
  * 5 (+): pp_batch_paths / pp_star_paths added, nothing else changed
  * 5 (+): pp_rrt_revalidate / pp_batch_revalidate added (a tree kept across a scene change),
- *    nothing else changed */
+ *    nothing else changed
+ * 5 (+): pp_star_revalidate added (the RRT* batch's trees kept across a scene change), nothing
+ *    else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -254,7 +256,7 @@ int pp_rrt_verify_node_batch(pp_ctx* ctx, const double* x, const double* y,
  * goal, step size, window and statistics stay; what pp_rrt_new derives from the scene is derived
  * again.  *n_kept (may be NULL) = the nodes that stay; new_index (may be NULL): one entry per node
  * before the call, its index afterwards or -1 when dropped.  PP_ERR_STATE without a tree;
- * PP_ERR_STEER_OVERFLOW leaves the tree unmodified.  RRT* batches are not covered. */
+ * PP_ERR_STEER_OVERFLOW leaves the tree unmodified.  (The RRT* batch: pp_star_revalidate.) */
 int pp_rrt_revalidate(pp_ctx* ctx, int64_t* n_kept, int32_t* new_index);
 
 /* --------------------------------------------------- goal connection (src/rrt.rs:428-619) */
@@ -366,7 +368,10 @@ int pp_batch_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* y
 int pp_star_new(pp_ctx* ctx, int q, const double* starts, const uint64_t* seeds,
                 int64_t max_iter, double step_size, int k, double eta);
 /* n_steps lockstep steps: every query runs one RRT* iteration per step until max_iter.  Batch
- * totals (each may be NULL): iterations, inserted nodes, rewires. */
+ * totals (each may be NULL): iterations, inserted nodes, rewires.  A later pp_space_new,
+ * pp_space_new_polygons or pp_space_set_grid does not invalidate the RRT* batch: this call,
+ * pp_star_plan and pp_star_paths keep working, but until pp_star_revalidate has run the trees are
+ * unverified in the new scene (they may hold edges through its obstacles). */
 int pp_star_extend(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t* n_accepted,
                    int64_t* n_rewires);
 /* per-query tree sizes (q int32), iterations, NN node-distance evaluations and rewires (q int64
@@ -376,6 +381,28 @@ int pp_star_state(pp_ctx* ctx, int32_t* n_nodes, int64_t* iterations, int64_t* n
 /* one query's tree (root first): coordinates, yaw, parent (-1 root) and node cost (root 0) */
 int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* yaw,
                         int32_t* parent, double* cost, int64_t cap, int64_t* n);
+/* Re-verify every query's tree of the RRT* batch against the context's current Space and drop
+ * what no longer holds (build-defined; CPU restatement
+ * tests/star_revalidate_ref.py).  The edge of node i > 0 is RRT*'s feasible edge (§3.7) from its
+ * stored pose to its parent's stored pose: the Dubins word is Some and Space::verify accepts the
+ * edge's points followed by the parent's point.  The stored yaw is the edge's own for an inserted
+ * node (compute_yaw toward the parent it chose) and for a rewired node (it kept its pose).  A None
+ * steer is an infeasible edge (not pp_rrt_revalidate's two-point line); it cannot occur in a tree
+ * this library grew — the word does not depend on the scene and every tree edge was feasible when
+ * it was made — so the device reports for it whatever its steer round does.  A node stays when
+ * every edge on its chain to the root is feasible; the chain is not index-ordered (a rewired
+ * node's parent is the later node that rewired it).  The root always stays; in polygon mode a root
+ * that fails verify as a point drops every other node and the query never inserts again.  Kept
+ * nodes keep their order and their pose, cost and edge cost bit for bit (dropping other nodes
+ * changes no kept node's cost); parents are remapped and may still exceed their child's index.
+ * The iteration counters, seeds, k, eta, step size, per-query evaluations and rewires and the
+ * statistics stay.  Accepted on any valid RRT* batch.  Outputs as pp_batch_revalidate's: n_nodes
+ * (q, may be NULL): the tree sizes after the call; *n_dropped (may be NULL): the nodes dropped
+ * over the batch; new_index (may be NULL): the sum of the old tree sizes, query i's entries at the
+ * prefix sum of pp_star_state's n_nodes read before the call, each a node's index in its tree
+ * afterwards or -1.  PP_ERR_STATE without an RRT* batch or a scene; PP_ERR_STEER_OVERFLOW leaves
+ * every tree unmodified. */
+int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_t* new_index);
 /* Goal connection (build-defined; CPU restatement tests/star_goal_ref.py).  The
  * goal edge of tree node m: the goal (gx, gy, gyaw) is the child and keeps its yaw, node m is the
  * parent — Dubins from the goal pose to the node's stored pose; feasible when the word is Some and

@@ -401,7 +401,8 @@ struct StarBatch {
     DBuf<long long> gsteer;
 };
 
-// ---- revalidation (pp_rrt_revalidate / pp_batch_revalidate: RevalArgs), reserved on first use
+// ---- revalidation (pp_rrt_revalidate / pp_batch_revalidate / pp_star_revalidate: RevalArgs),
+// reserved on first use
 constexpr int kRevalSlice = 32768;  // steer tasks per slice
 struct Reval {
     DBuf<SteerTask> tasks;
@@ -409,6 +410,7 @@ struct Reval {
     DBuf<PrepRec> rec;
     DBuf<int> status, off, bsum, pos, new_index, spar, err;
     DBuf<double> yaw, sx, sy, syaw;
+    DBuf<double> scost, selen;  // RRT* only
     DBuf<long long> srow;
     DBuf<unsigned> v0, v1;
     DBuf<uint8_t> blocked;

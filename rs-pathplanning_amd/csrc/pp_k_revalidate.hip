@@ -1,18 +1,25 @@
 // pp_k_revalidate.hip — re-verify a tree (or a forest of per-query trees) against the current
-// scene and drop what no longer verifies (pp_rrt_revalidate / pp_batch_revalidate).
+// scene and drop what no longer verifies (pp_rrt_revalidate / pp_batch_revalidate /
+// pp_star_revalidate).
 //
 // Node g of the `total` nodes (tree q's nodes at off[q] .. off[q + 1], row q * cap + i) keeps its
 // place exactly when its own edge verifies and its parent keeps its place (RRT::verify_node's
 // line_to_origin decomposes over the edges).  In stream order, no host round trip:
 //   emit      one explicit steer task per node of a slice: the child keeps its stored yaw
-//             (own_yaw), the parent pose comes from the parent's row, no cull
+//             (own_yaw), the parent pose comes from the parent's row, no cull.  A parent is an
+//             earlier node of the tree; with any_order (RRT*: a rewired node hangs under the
+//             later node that rewired it) any other node of the tree
 //   prep/walk the steer round of pp_steer_launch.h on the slice (kWalkBatchPlan)
 //   settle    literal-path verdicts re-run (slot-locked scratch pool); v[g] = ancestor | bad << 31
 //   jump      pointer doubling over the ping-pong v arrays: after k passes v[g] covers the 2^k
-//             edges above g; parents precede children, so ceil(log2(largest tree)) passes are exact
+//             edges above g.  Doubling needs no index order: a tree is acyclic, so a chain has
+//             at most n - 1 edges wherever its parents sit, and ceil(log2(largest tree)) passes
+//             are exact.  any_order: a chain that does not end in its tree's root (a cyclic
+//             parent array) is dropped
 //   scan      exclusive scan of keep over all nodes (per-workgroup counts, their scan, positions);
 //             a tree's new indices are the positions less the position of its root
-//   gather    kept rows into a compact staging copy with remapped parents, new_index
+//   gather    kept rows (RRT*: with their cost / elen) into a compact staging copy with remapped
+//             parents, new_index
 //   write     staging back into the trees' rows (skipped when a steer overflowed: the trees stay)
 #include <hip/hip_runtime.h>
 
@@ -53,13 +60,15 @@ __global__ __launch_bounds__(kRvThreads) void reval_emit_kernel(RevalArgs a, int
     const size_t o = (size_t)q * a.cap;
     SteerTask tk{};
     StarTaskExt ex{};
-    tk.pnode = -1;  // (idle: the root, or a parent index that is no earlier node)
+    tk.pnode = -1;  // (idle: the root, or a parent index that is no earlier / no other node)
     ex.own_yaw = 1;
     ex.node = i;
     ex.pad = q;
     if (i > 0) {
         const int p = a.tr.parent[o + i];
-        if (p >= 0 && p < i) {
+        const bool live = a.any_order ? p >= 0 && p < a.off[q + 1] - a.off[q] && p != i
+                                      : p >= 0 && p < i;
+        if (live) {
             tk.x = a.tr.x[o + i];
             tk.y = a.tr.y[o + i];
             tk.px = a.tr.x[o + p];
@@ -129,15 +138,24 @@ __global__ __launch_bounds__(kRvThreads) void reval_jump_kernel(const unsigned* 
     out[g] = (w & ~kRvBad) | ((v | w) & kRvBad);
 }
 
-// a root's ancestor is itself (every other node's is an earlier node)
-__device__ inline bool rv_keep(unsigned v, int g) {
-    return !(v & kRvBad) || (v & ~kRvBad) == (unsigned)g;
+// a root's ancestor is itself (every other node's is an earlier node).  off != null (any_order):
+// parents come in any order, so the final ancestor must also be the root of g's tree — a chain
+// that never reaches it is dropped, not kept
+__device__ inline bool rv_keep(unsigned v, int g, const int* __restrict__ off, int Q) {
+    const unsigned anc = v & ~kRvBad;
+    if (off) {
+        const unsigned g0 = (unsigned)off[rv_tree_of(off, Q, g)];
+        return anc == g0 && (!(v & kRvBad) || (unsigned)g == g0);
+    }
+    return !(v & kRvBad) || anc == (unsigned)g;
 }
 
+// (off / Q: rv_keep's, null / 0 unless any_order)
 __global__ __launch_bounds__(kRvScan) void reval_count_kernel(const unsigned* __restrict__ v,
-                                                             int total, int* __restrict__ bsum) {
+                                                             int total, int* __restrict__ bsum,
+                                                             const int* __restrict__ off, int Q) {
     const int g = blockIdx.x * kRvScan + threadIdx.x;
-    const int c = __syncthreads_count(g < total && rv_keep(v[g < total ? g : 0], g));
+    const int c = __syncthreads_count(g < total && rv_keep(v[g < total ? g : 0], g, off, Q));
     if (threadIdx.x == 0) bsum[blockIdx.x] = c;
 }
 
@@ -181,9 +199,10 @@ __global__ __launch_bounds__(kRvScan) void reval_bscan_kernel(int* __restrict__ 
 
 __global__ __launch_bounds__(kRvScan) void reval_pos_kernel(const unsigned* __restrict__ v,
                                                            int total, const int* __restrict__ bsum,
-                                                           int* __restrict__ pos) {
+                                                           int* __restrict__ pos,
+                                                           const int* __restrict__ off, int Q) {
     const int g = blockIdx.x * kRvScan + threadIdx.x;
-    const int k = g < total && rv_keep(v[g < total ? g : 0], g) ? 1 : 0;
+    const int k = g < total && rv_keep(v[g < total ? g : 0], g, off, Q) ? 1 : 0;
     int sum;
     const int e = bsum[blockIdx.x] + rv_block_scan(k, &sum);
     if (g < total) pos[g] = e;
@@ -194,7 +213,7 @@ __global__ __launch_bounds__(kRvThreads) void reval_gather_kernel(RevalArgs a,
                                                                  const unsigned* __restrict__ v) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.total) return;
-    if (!rv_keep(v[g], g)) {
+    if (!rv_keep(v[g], g, a.any_order ? a.off : nullptr, a.Q)) {
         a.new_index[g] = -1;
         return;
     }
@@ -209,8 +228,15 @@ __global__ __launch_bounds__(kRvThreads) void reval_gather_kernel(RevalArgs a,
     // (a kept node's parent is kept)
     a.spar[k] = i == 0 ? -1 : a.pos[g0 + a.tr.parent[o + i]] - a.pos[g0];
     a.srow[k] = (long long)(o + j);
+    if (a.cost) {  // RRT*: dropping other nodes changes no kept node's cost
+        a.scost[k] = a.cost[o + i];
+        a.selen[k] = a.elen[o + i];
+    }
 }
 
+// RRT*'s mark[] / stamp[] stay as they are: star_rewire_kernel compares a mark only for equality
+// with the current stamp and relies on mark[row] < stamp[q] for every row of query q alone, which
+// holds before the call and so after any move of rows (rows past the new n keep their contents)
 __global__ __launch_bounds__(kRvThreads) void reval_write_kernel(RevalArgs a) {
     if (*a.err) return;  // a steer overflowed: the trees stay as they are
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -222,6 +248,10 @@ __global__ __launch_bounds__(kRvThreads) void reval_write_kernel(RevalArgs a) {
     a.tr.y[row] = y;
     a.tr.yaw[row] = a.syaw[k];
     a.tr.parent[row] = a.spar[k];
+    if (a.cost) {
+        a.cost[row] = a.scost[k];
+        a.elen[row] = a.selen[k];
+    }
     if (a.tr.x32) {  // the one-tree planner's f32 screen copies
         a.tr.x32[row] = (float)x;
         a.tr.y32[row] = (float)y;
@@ -246,9 +276,10 @@ hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs&
         reval_jump_kernel<<<g, kRvThreads, 0, s>>>(a.v[p & 1], a.v[(p + 1) & 1], a.total);
     const unsigned* v = a.v[passes & 1];
     const int nb = (a.total + kRvScan - 1) / kRvScan;
-    reval_count_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum);
+    const int* koff = a.any_order ? a.off : nullptr;
+    reval_count_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum, koff, a.Q);
     reval_bscan_kernel<<<1, kRvScan, 0, s>>>(a.bsum, nb);
-    reval_pos_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum, a.pos);
+    reval_pos_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum, a.pos, koff, a.Q);
     reval_gather_kernel<<<g, kRvThreads, 0, s>>>(a, v);
     reval_write_kernel<<<(std::max(a.total, a.Q) + kRvThreads - 1) / kRvThreads, kRvThreads, 0, s>>>(a);
     return hipGetLastError();

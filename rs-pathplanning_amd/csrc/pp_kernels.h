@@ -290,9 +290,9 @@ struct StarGoalArgs {
 };
 hipError_t launch_star_goal(hipStream_t s, const StarGoalArgs& g, int rounds);
 
-// Revalidation (pp_rrt_revalidate / pp_batch_revalidate, pp_k_revalidate.hip): re-verify every
-// node's edge against the scene, propagate failures to the descendants and compact the trees in
-// place.  `total` nodes in Q trees: tree q's nodes are g = off[q] .. off[q + 1] - 1, node i of it
+// Revalidation (pp_rrt_revalidate / pp_batch_revalidate / pp_star_revalidate,
+// pp_k_revalidate.hip): re-verify every node's edge against the scene, propagate failures to the
+// descendants and compact the trees in place.  `total` nodes in Q trees: tree q's nodes are g = off[q] .. off[q + 1] - 1, node i of it
 // in row q * cap + i of tr (x32 / y32 null: a forest without screen copies).
 struct RevalArgs {
     TreeDev tr{};
@@ -302,6 +302,11 @@ struct RevalArgs {
     int total = 0;                     // off[Q]
     const uint8_t* blocked = nullptr;  // [Q] the root fails verify (polygon mode; may be null)
     int* n = nullptr;                  // [Q] the trees' node counts, rewritten (may be null)
+    // RRT* (pp_star_revalidate): a node's parent is any other node of its tree (a rewired node
+    // hangs under a later one), and a chain that does not end in the tree's root is dropped
+    int any_order = 0;
+    double* cost = nullptr;  // RRT*'s per-row arrays, carried with the rows (null: none)
+    double* elen = nullptr;
     // one slice of steer tasks at a time
     int slice = 0;
     SteerTask* tasks = nullptr;
@@ -318,6 +323,8 @@ struct RevalArgs {
     double* sy = nullptr;
     double* syaw = nullptr;
     int* spar = nullptr;
+    double* scost = nullptr;  // (cost != null)
+    double* selen = nullptr;
     long long* srow = nullptr;  // ... and the row each goes back to
     int* err = nullptr;         // != 0: a steer overflowed n_point; the trees are left as they are
     double* lit_scratch = nullptr;  // kLiteralWaves buffers

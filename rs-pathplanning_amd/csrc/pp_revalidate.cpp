@@ -1,7 +1,8 @@
-// pp_revalidate.cpp — a tree across a scene change: pp_rrt_revalidate and pp_batch_revalidate
-// re-verify the tree(s) on the device against the context's current Space, drop every node whose
-// line_to_origin no longer verifies and derive again what pp_rrt_new / pp_batch_new derive from
-// the scene.
+// pp_revalidate.cpp — a tree across a scene change: pp_rrt_revalidate, pp_batch_revalidate and
+// pp_star_revalidate re-verify the tree(s) on the device against the context's current Space, drop
+// every node whose line_to_origin (RRT*: whose chain of stored edges to the root) no longer
+// verifies and derive again what pp_rrt_new / pp_batch_new / pp_star_new derive from the scene
+// (DESIGN.md §3.8).
 #include "pp_ctx.h"
 
 using namespace ppamd;
@@ -11,10 +12,12 @@ namespace {
 // The device pass over Q trees of hn[q] nodes in the rows tr (tree q at q * cap): *kept the nodes
 // that stay over all trees; new_index (may be null) the sum of hn entries.  blocked (host, may be
 // null): the roots that fail verify.  d_n (may be null): the trees' node counts on the device.
+// any_order with the cost / elen rows: an RRT* forest (RevalArgs), else false and null.
 // One synchronisation; on PP_ERR_STEER_OVERFLOW the trees are unmodified.
 int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t cap,
               const std::vector<int>& hn, const uint8_t* blocked, int* d_n, int64_t* kept,
-              int32_t* new_index) {
+              int32_t* new_index, bool any_order = false, double* cost = nullptr,
+              double* elen = nullptr) {
     Reval& r = c->reval;
     std::vector<int> off((size_t)Q + 1, 0);
     int64_t total64 = 0;
@@ -42,6 +45,8 @@ int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t ca
     PP_HIP(r.pos.reserve(z + 1));
     for (auto* b : {&r.new_index, &r.spar}) PP_HIP(b->reserve(z));
     for (auto* b : {&r.sx, &r.sy, &r.syaw}) PP_HIP(b->reserve(z));
+    if (cost)
+        for (auto* b : {&r.scost, &r.selen}) PP_HIP(b->reserve(z));
     PP_HIP(r.srow.reserve(z));
     PP_HIP(r.v0.reserve(z));
     PP_HIP(r.v1.reserve(z));
@@ -61,6 +66,11 @@ int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t ca
     a.total = total;
     a.blocked = blocked ? r.blocked.p : nullptr;
     a.n = d_n;
+    a.any_order = any_order ? 1 : 0;
+    a.cost = cost;
+    a.elen = elen;
+    a.scost = cost ? r.scost.p : nullptr;
+    a.selen = cost ? r.selen.p : nullptr;
     a.slice = slice;
     a.tasks = r.tasks.p;
     a.ext = r.ext.p;
@@ -82,7 +92,7 @@ int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t ca
     a.lit_scratch = c->api_lit_scratch.p;
     a.lit_locks = c->lit_locks.p;
     a.wg_points = c->prof.points();
-    // parents precede children: a tree of n nodes is at most n - 1 edges deep
+    // a tree of n nodes is at most n - 1 edges deep, whatever the order of its parents
     int passes = 0;
     while (((int64_t)1 << passes) < nmax) ++passes;
     PP_HIP(launch_revalidate(st, sc, a, passes));
@@ -183,6 +193,49 @@ int pp_batch_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32
     PP_HIP(hipStreamSynchronize(st));
     b.stale = false;
     b.valid = true;
+    if (n_dropped) *n_dropped = total - kept;
+    return PP_OK;
+}
+
+int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_t* new_index) {
+    int rc = check_ctx(ctx, true, false);
+    if (rc) return rc;
+    StarBatch& s = ctx->star;
+    if (!s.valid) return set_err(PP_ERR_STATE, "no RRT* batch to revalidate: pp_star_new has not been called");
+    Forest& f = s.f;
+    const int Q = f.Q;
+    hipStream_t st = ctx->stream;
+    std::vector<int> hn((size_t)Q);
+    std::vector<double> starts(3 * (size_t)Q);
+    PP_HIP(hipMemcpyAsync(hn.data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(starts.data(), f.d_starts.p, starts.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    // the roots that fail verify in the scene as it is now (Forest::init)
+    std::vector<uint8_t> blk((size_t)Q, 0);
+    bool any = false;
+    if (ctx->scene.polygons())
+        for (int q = 0; q < Q; ++q) {
+            blk[(size_t)q] = ctx->scene.point_ok(starts[3 * (size_t)q], starts[3 * (size_t)q + 1]) ? 0 : 1;
+            any |= blk[(size_t)q] != 0;
+        }
+    SceneDev sc = ctx->scene_dev();  // the scene of the batch's own steer rounds (star_args)
+    sc.step_size = f.step;
+    int64_t kept = 0, total = 0;
+    for (int q = 0; q < Q; ++q) total += hn[(size_t)q];
+    // a rewired node hangs under the later node that rewired it: parents in any order; cost and
+    // elen travel with the rows, mark / stamp stay (reval_write_kernel)
+    if ((rc = reval_run(ctx, sc, f.tree_dev(), Q, (size_t)f.cap, hn, any ? blk.data() : nullptr,
+                        f.n.p, &kept, new_index, true, s.cost.p, s.elen.p)))
+        return rc;
+    if (any) {
+        PP_HIP(f.blocked.reserve(Q));
+        PP_HIP(hipMemcpy(f.blocked.p, blk.data(), Q, hipMemcpyHostToDevice));
+    }
+    f.any_blocked = any;
+    if (n_nodes) {
+        PP_HIP(hipMemcpyAsync(n_nodes, f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+        PP_HIP(hipStreamSynchronize(st));
+    }
     if (n_dropped) *n_dropped = total - kept;
     return PP_OK;
 }

@@ -47,7 +47,7 @@ EXPORTED = [
     "pp_rrt_plan", "pp_batch_new", "pp_batch_set_window", "pp_batch_set_finish_schedule", "pp_batch_extend", "pp_batch_state", "pp_batch_tree_export",
     "pp_batch_plan", "pp_batch_paths",
     "pp_rrt_revalidate", "pp_batch_revalidate",
-    "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export",
+    "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export", "pp_star_revalidate",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
 ]
@@ -176,6 +176,7 @@ def lib():
             "pp_star_new": ([vp, C.c_int, dp, C.POINTER(C.c_uint64), C.c_int64, C.c_double,
                              C.c_int, C.c_double], C.c_int),
             "pp_star_extend": ([vp, C.c_int64, i64p, i64p, i64p], C.c_int),
+            "pp_star_revalidate": ([vp, ip, i64p, ip], C.c_int),
             "pp_star_state": ([vp, ip, i64p, i64p, i64p], C.c_int),
             "pp_star_tree_export": ([vp, C.c_int, dp, dp, dp, ip, dp, C.c_int64, i64p], C.c_int),
             "pp_star_plan": ([vp, dp, ip, dp, i64p], C.c_int),

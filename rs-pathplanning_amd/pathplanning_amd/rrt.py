@@ -688,6 +688,35 @@ class RRTStarBatch:
             C.byref(out)))
         return x, y, yaw, par, cost
 
+    def revalidate(self, n_old=None):
+        """Re-verify every query's tree against the context's current scene (pp_star_revalidate)
+        and drop the nodes whose chain of stored edges to the root no longer holds: RRT*'s
+        feasible edge per node, chains in any index order (a rewired node's parent is a later
+        node).  Kept nodes keep their order, pose and cost; parents are remapped.  Returns
+        (n_nodes int32[q] after the call, new_index int32[sum of the old sizes]): query q's
+        entries start at the prefix sum of the old sizes, each a node's index in its tree
+        afterwards or -1.  ``n_old``: the old sizes, when already known.  ``last_dropped``: the
+        nodes dropped over the batch."""
+        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
+        total = int(n_old.sum(dtype=np.int64))
+        new_index = np.zeros(max(total, 1), dtype=np.int32)
+        n = np.zeros(self.q, dtype=np.int32)
+        dropped = C.c_int64(0)
+        ip = C.POINTER(C.c_int32)
+        _ffi.check(_ffi.lib().pp_star_revalidate(
+            self.ctx.handle, n.ctypes.data_as(ip), C.byref(dropped), new_index.ctypes.data_as(ip)))
+        self.last_dropped = dropped.value
+        return n, new_index[:total]
+
+    def set_space(self, space: Space):
+        """Replace the scene of the batch and keep every tree where it still holds: uploads
+        ``space`` into the batch's context and revalidates.  (Uploading a scene alone does not
+        stop the batch: its trees are unverified until ``revalidate``.)"""
+        n_old = self.state()[0]
+        space._upload(self.ctx)
+        self.space = space
+        return self.revalidate(n_old)
+
     # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path, DESIGN.md §3.7)
     def plan(self, goals):
         """The cheapest feasible goal edge of every query on its tree as extended so far: goal
