@@ -38,7 +38,9 @@ extern "C" {
  * 5 (+): pp_rrt_revalidate / pp_batch_revalidate added (a tree kept across a scene change),
  *    nothing else changed
  * 5 (+): pp_star_revalidate added (the RRT* batch's trees kept across a scene change), nothing
- *    else changed */
+ *    else changed
+ * 5 (+): pp_star_repair added (dropped subtrees re-attached under kept nodes after a scene
+ *    change), nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -401,8 +403,31 @@ int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* ya
  * over the batch; new_index (may be NULL): the sum of the old tree sizes, query i's entries at the
  * prefix sum of pp_star_state's n_nodes read before the call, each a node's index in its tree
  * afterwards or -1.  PP_ERR_STATE without an RRT* batch or a scene; PP_ERR_STEER_OVERFLOW leaves
- * every tree unmodified. */
+ * every tree unmodified.  (A dropped subtree whose top still reaches a kept node is lost here;
+ * pp_star_repair hangs it back.) */
 int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_t* new_index);
+/* pp_star_revalidate with up to `rounds` re-attachment rounds before the compaction (build-defined,
+ * DESIGN.md §3.8; CPU restatement tests/star_repair_ref.py).  rounds = 0 is pp_star_revalidate,
+ * result for result.  Round r (for as long as it has tops): a top is a dropped node that was no
+ * top before and whose own edge fails (r = 1) or whose parent was a top of an earlier round that
+ * found no parent (r > 1).  A top's candidates are the star_k(k, |K|) nearest nodes of its point
+ * by (squared distance, index before the call) among the set K kept at the start of the round;
+ * the edge top -> candidate keeps the top's stored pose (like a rewire), is feasible as above, and
+ * total = cost[candidate] + its Dubins cost with the costs of the start of the round.  The first
+ * strict minimum of total in candidate order becomes the top's parent (its edge cost and cost
+ * with it); a top without a feasible candidate is dropped for good.  Every dropped node whose
+ * chain of feasible stored edges reaches a re-attached top is kept again: its edge cost stays,
+ * its cost becomes cost[parent] + edge cost, parents before children.  Tops read the start-of-
+ * round state only, so the result does not depend on their order.  A root-blocked query (polygon
+ * mode) re-attaches nothing.  Nodes pp_star_revalidate keeps keep cost and edge cost bit for bit;
+ * compaction, counters and the derived state are pp_star_revalidate's.  rounds outside [0, 16]:
+ * PP_ERR_INVALID_ARGUMENT.  n_nodes, n_dropped, new_index: as pp_star_revalidate's (each may be
+ * NULL).  *n_reattached (may be NULL): the tops that found a parent; *n_recovered (may be NULL):
+ * the nodes kept that pp_star_revalidate would have dropped, those tops included.  PP_ERR_STATE
+ * without an RRT* batch or a scene; PP_ERR_STEER_OVERFLOW leaves every tree unmodified.  The host
+ * synchronises once per round run (to read the round's top count), and once more at the end. */
+int pp_star_repair(pp_ctx* ctx, int rounds, int32_t* n_nodes, int64_t* n_dropped,
+                   int64_t* n_reattached, int64_t* n_recovered, int32_t* new_index);
 /* Goal connection (build-defined; CPU restatement tests/star_goal_ref.py).  The
  * goal edge of tree node m: the goal (gx, gy, gyaw) is the child and keeps its yaw, node m is the
  * parent — Dubins from the goal pose to the node's stored pose; feasible when the word is Some and

@@ -7,7 +7,9 @@
 //   pp_batch.cpp    the forest of per-query trees, pp_batch_*, pp_star_*
 //   pp_star_goal.cpp  the RRT* goal connection: pp_star_plan, pp_star_goal_costs, pp_star_path,
 //                     pp_star_paths
-//   pp_revalidate.cpp  a tree across a scene change: pp_rrt_revalidate, pp_batch_revalidate
+//   pp_revalidate.cpp  a tree across a scene change: pp_rrt_revalidate, pp_batch_revalidate,
+//                      pp_star_revalidate
+//   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -415,6 +417,12 @@ struct Reval {
     DBuf<unsigned> v0, v1;
     DBuf<uint8_t> blocked;
     DBuf<DevState> state;
+    // pp_star_repair only (RepairArgs)
+    DBuf<unsigned> vedge;
+    DBuf<unsigned char> flag, top, qhas;
+    DBuf<int> lvl, wpar, tops, tslot, tcnt, near;
+    DBuf<double> wcost, welen, tcost;
+    DBuf<RepairRec> rrec;
 };
 
 // ---- profiling
@@ -499,5 +507,20 @@ int paths_line_buffers(pp_ctx* c, int k, CfLines& lines);
 int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines,
                 const int* items, int k, bool star, double* x, double* y, int64_t total,
                 double* len_host = nullptr);
+// The two host halves of a revalidation around its launches (pp_revalidate.cpp), shared with
+// pp_star_repair (pp_repair.cpp).  reval_setup: the buffers (the steer slice's for at least
+// min_tasks tasks), the offsets and blocked roots on the device, the kernel arguments and the
+// doubling passes, for Q trees of hn[q] nodes in the rows tr (tree q at q * cap).  reval_finish:
+// the kept nodes over all trees, new_index (may be null) and the error word after one
+// synchronisation; PP_ERR_STEER_OVERFLOW when a steer overflowed (the trees are unmodified).
+int reval_setup(pp_ctx* c, const TreeDev& tr, int Q, size_t cap, const std::vector<int>& hn,
+                const uint8_t* blocked, int* d_n, bool any_order, double* cost, double* elen,
+                int min_tasks, RevalArgs* a, int* passes);
+int reval_finish(pp_ctx* c, const RevalArgs& a, int64_t* kept, int32_t* new_index);
+// what pp_star_revalidate and pp_star_repair read first: the trees' sizes and, in polygon mode,
+// the roots that fail verify in the scene as it is now (*any: at least one does)
+int star_reval_inputs(pp_ctx* c, std::vector<int>* hn, std::vector<uint8_t>* blk, bool* any);
+// ... and what both leave behind: the derived blocked[] and the sizes for the caller
+int star_reval_outputs(pp_ctx* c, const std::vector<uint8_t>& blk, bool any, int32_t* n_nodes);
 
 }  // namespace ppamd

@@ -26,25 +26,13 @@
 #include <algorithm>
 
 #include "pp_kernels.h"
+#include "pp_reval_dev.h"
 #include "pp_steer_dev.h"
 #include "pp_steer_launch.h"
 
 namespace ppamd {
 
-constexpr unsigned kRvBad = 0x80000000u;
-constexpr int kRvThreads = 256;
 constexpr int kRvScan = 1024;  // nodes per scan workgroup
-
-// the tree of node g: the last q with off[q] <= g
-__device__ inline int rv_tree_of(const int* __restrict__ off, int Q, int g) {
-    int lo = 0, hi = Q;  // off[lo] <= g < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(kRvThreads) void reval_emit_kernel(RevalArgs a, int base, int count) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,18 +124,6 @@ __global__ __launch_bounds__(kRvThreads) void reval_jump_kernel(const unsigned* 
     const unsigned v = in[g];
     const unsigned w = in[v & ~kRvBad];
     out[g] = (w & ~kRvBad) | ((v | w) & kRvBad);
-}
-
-// a root's ancestor is itself (every other node's is an earlier node).  off != null (any_order):
-// parents come in any order, so the final ancestor must also be the root of g's tree — a chain
-// that never reaches it is dropped, not kept
-__device__ inline bool rv_keep(unsigned v, int g, const int* __restrict__ off, int Q) {
-    const unsigned anc = v & ~kRvBad;
-    if (off) {
-        const unsigned g0 = (unsigned)off[rv_tree_of(off, Q, g)];
-        return anc == g0 && (!(v & kRvBad) || (unsigned)g == g0);
-    }
-    return !(v & kRvBad) || anc == (unsigned)g;
 }
 
 // (off / Q: rv_keep's, null / 0 unless any_order)
@@ -258,7 +234,10 @@ __global__ __launch_bounds__(kRvThreads) void reval_write_kernel(RevalArgs a) {
     }
 }
 
-hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs& a, int passes) {
+// The three stages of a revalidation, so that pp_star_repair can work between the jump and the
+// compaction: the edge test into a.v[0], the doubling into a.v[passes & 1], the compaction of the
+// nodes rv_keep keeps in v.
+hipError_t launch_reval_edges(hipStream_t s, const SceneDev& sc, const RevalArgs& a) {
     if (a.total <= 0 || a.slice <= 0) return hipErrorInvalidValue;
     const int limit = walk_grid_limit(kWalkBatchPlan, sc);
     for (int base = 0; base < a.total; base += a.slice) {
@@ -271,10 +250,18 @@ hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs&
         const int waves = (count + 63) / 64;
         reval_settle_kernel<<<std::min((waves + 3) / 4, 1024), kRvThreads, 0, s>>>(a, sc, base);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_reval_jump(hipStream_t s, const RevalArgs& a, int passes) {
     const int g = (a.total + kRvThreads - 1) / kRvThreads;
     for (int p = 0; p < passes; ++p)
         reval_jump_kernel<<<g, kRvThreads, 0, s>>>(a.v[p & 1], a.v[(p + 1) & 1], a.total);
-    const unsigned* v = a.v[passes & 1];
+    return hipGetLastError();
+}
+
+hipError_t launch_reval_compact(hipStream_t s, const RevalArgs& a, const unsigned* v) {
+    const int g = (a.total + kRvThreads - 1) / kRvThreads;
     const int nb = (a.total + kRvScan - 1) / kRvScan;
     const int* koff = a.any_order ? a.off : nullptr;
     reval_count_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum, koff, a.Q);
@@ -283,6 +270,13 @@ hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs&
     reval_gather_kernel<<<g, kRvThreads, 0, s>>>(a, v);
     reval_write_kernel<<<(std::max(a.total, a.Q) + kRvThreads - 1) / kRvThreads, kRvThreads, 0, s>>>(a);
     return hipGetLastError();
+}
+
+hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs& a, int passes) {
+    hipError_t e = launch_reval_edges(s, sc, a);
+    if (e != hipSuccess) return e;
+    if ((e = launch_reval_jump(s, a, passes)) != hipSuccess) return e;
+    return launch_reval_compact(s, a, a.v[passes & 1]);
 }
 
 }  // namespace ppamd

@@ -333,6 +333,58 @@ struct RevalArgs {
 };
 // passes: ceil(log2(the largest tree's node count)) pointer-doubling passes
 hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs& a, int passes);
+// ... and its three stages (launch_revalidate runs them in this order): the edge test of every
+// node into a.v[0], the doubling into a.v[passes & 1], and the compaction of the nodes whose word
+// in v keeps them (rv_keep)
+hipError_t launch_reval_edges(hipStream_t s, const SceneDev& sc, const RevalArgs& a);
+hipError_t launch_reval_jump(hipStream_t s, const RevalArgs& a, int passes);
+hipError_t launch_reval_compact(hipStream_t s, const RevalArgs& a, const unsigned* v);
+
+// Repair (pp_star_repair, pp_k_repair.hip): between the jump and the compaction
+// of an RRT* forest's revalidation, dropped subtrees are hung under kept nodes again, in rounds.
+// All per-node arrays are indexed by the global node g of RevalArgs.
+constexpr int kRepairMaxRounds = 16;
+constexpr int kRepairTopsPerSlice = 512;  // <= 512 * kStarKMax tasks a steer slice
+enum : unsigned char { kTopNever = 0, kTopNow = 1, kTopAttached = 2, kTopFailed = 3 };
+struct RepairRec {  // the counters the host reads
+    int ntops[kRepairMaxRounds + 1];  // [r]: the tops of round r
+    long long reattached, recovered;
+};
+struct RepairArgs {
+    RevalArgs rv;  // the forest, its offsets, the steer slice's buffers (>= kRepairTopsPerSlice *
+                   // kStarKMax tasks), the literal pool and the error word
+    const int* ksched = nullptr;     // [cap + 1] star_k of the batch over the kept count
+    const unsigned* vedge = nullptr; // [total] the settle's words: bad = the node's own edge fails
+    const unsigned* vkeep = nullptr; // [total] the words after the jump: K0 by rv_keep
+    unsigned* vout = nullptr;        // [total] the words the compaction keeps by (repair_commit)
+    unsigned char* flag = nullptr;   // [total] bit 0: kept, bit 1: kept by the repair
+    unsigned char* top = nullptr;    // [total] kTopNever .. kTopFailed
+    int* lvl = nullptr;              // [total] the round's levels: 1 a re-attached top, d + 1 its
+                                     // descendants at depth d (zeroed before every round)
+    int* wpar = nullptr;             // [total] parent (index in its tree), staged
+    double* wcost = nullptr;         // [total] cost, staged
+    double* welen = nullptr;         // [total] elen, staged
+    double* tcost = nullptr;         // [slice tasks] the Dubins cost of each task
+    int* tops = nullptr;             // [total] the round's tops, packed
+    int* near = nullptr;             // [round's tops * kStarKMax] a top's candidates in (d2, index) order
+    int* tcnt = nullptr;             // [round's tops] ... and their count
+    int* tslot = nullptr;            // [kRepairTopsPerSlice] first task of a slice's top
+    unsigned char* qhas = nullptr;   // [Q] the query re-attached a top this round (zeroed per round)
+    RepairRec* rec = nullptr;
+};
+enum : int { kRepairInit = 0, kRepairTops, kRepairGrow, kRepairCommit };
+// one stage over all nodes: init (the staged copies, K0), tops (mark and pack round `round`'s
+// tops, count them in rec->ntops[round]), grow (keep the subtrees under the re-attached tops
+// again, their costs level by level) and commit (the staged rows into the trees unless a steer
+// overflowed, the keep words into vout)
+hipError_t launch_repair_stage(hipStream_t s, const RepairArgs& a, int stage, int round);
+// the candidates of all `ntops` packed tops of the round: the kNN among the kept nodes, one wave
+// per top in one launch
+hipError_t launch_repair_knn(hipStream_t s, const RepairArgs& a, int ntops);
+// the steer round of the packed tops [t0, t1), t1 - t0 <= kRepairTopsPerSlice: their tasks, prep,
+// walk, choose
+hipError_t launch_repair_slice(hipStream_t s, const SceneDev& sc, const RepairArgs& a, int t0,
+                               int t1);
 
 // dubins_path_planning_from_origin for n (dx, dy, eyaw, c, step_size) configurations
 hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int cap, double* px,

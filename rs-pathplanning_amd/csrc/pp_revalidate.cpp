@@ -7,17 +7,11 @@
 
 using namespace ppamd;
 
-namespace {
+namespace ppamd {
 
-// The device pass over Q trees of hn[q] nodes in the rows tr (tree q at q * cap): *kept the nodes
-// that stay over all trees; new_index (may be null) the sum of hn entries.  blocked (host, may be
-// null): the roots that fail verify.  d_n (may be null): the trees' node counts on the device.
-// any_order with the cost / elen rows: an RRT* forest (RevalArgs), else false and null.
-// One synchronisation; on PP_ERR_STEER_OVERFLOW the trees are unmodified.
-int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t cap,
-              const std::vector<int>& hn, const uint8_t* blocked, int* d_n, int64_t* kept,
-              int32_t* new_index, bool any_order = false, double* cost = nullptr,
-              double* elen = nullptr) {
+int reval_setup(pp_ctx* c, const TreeDev& tr, int Q, size_t cap, const std::vector<int>& hn,
+                const uint8_t* blocked, int* d_n, bool any_order, double* cost, double* elen,
+                int min_tasks, RevalArgs* out, int* passes_out) {
     Reval& r = c->reval;
     std::vector<int> off((size_t)Q + 1, 0);
     int64_t total64 = 0;
@@ -33,11 +27,12 @@ int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t ca
     const int total = (int)total64;
     const size_t z = (size_t)total;
     const int slice = std::min(total, kRevalSlice);
-    PP_HIP(r.tasks.reserve(slice));
-    PP_HIP(r.ext.reserve(slice));
-    PP_HIP(r.rec.reserve(slice));
-    PP_HIP(r.status.reserve(slice));
-    PP_HIP(r.yaw.reserve(slice));
+    const int tasks = std::max(slice, min_tasks);
+    PP_HIP(r.tasks.reserve(tasks));
+    PP_HIP(r.ext.reserve(tasks));
+    PP_HIP(r.rec.reserve(tasks));
+    PP_HIP(r.status.reserve(tasks));
+    PP_HIP(r.yaw.reserve(tasks));
     PP_HIP(r.state.reserve(1));
     PP_HIP(r.err.reserve(1));
     PP_HIP(r.off.reserve((size_t)Q + 1));
@@ -95,7 +90,16 @@ int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t ca
     // a tree of n nodes is at most n - 1 edges deep, whatever the order of its parents
     int passes = 0;
     while (((int64_t)1 << passes) < nmax) ++passes;
-    PP_HIP(launch_revalidate(st, sc, a, passes));
+    *out = a;
+    *passes_out = passes;
+    return PP_OK;
+}
+
+int reval_finish(pp_ctx* c, const RevalArgs& a, int64_t* kept, int32_t* new_index) {
+    Reval& r = c->reval;
+    hipStream_t st = c->stream;
+    const int total = a.total;
+    const size_t z = (size_t)total;
     int h[2] = {0, 0};  // kept nodes, error word
     PP_HIP(hipMemcpyAsync(&h[0], r.pos.p + total, sizeof(int), hipMemcpyDeviceToHost, st));
     PP_HIP(hipMemcpyAsync(&h[1], r.err.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -107,6 +111,63 @@ int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t ca
                        "generate_local_course would index past n_point (the reference panics)");
     *kept = h[0];
     return PP_OK;
+}
+
+int star_reval_inputs(pp_ctx* c, std::vector<int>* hn, std::vector<uint8_t>* blk, bool* any) {
+    Forest& f = c->star.f;
+    const int Q = f.Q;
+    hipStream_t st = c->stream;
+    hn->assign((size_t)Q, 0);
+    std::vector<double> starts(3 * (size_t)Q);
+    PP_HIP(hipMemcpyAsync(hn->data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(starts.data(), f.d_starts.p, starts.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    // the roots that fail verify in the scene as it is now (Forest::init)
+    blk->assign((size_t)Q, 0);
+    *any = false;
+    if (c->scene.polygons())
+        for (int q = 0; q < Q; ++q) {
+            (*blk)[(size_t)q] = c->scene.point_ok(starts[3 * (size_t)q], starts[3 * (size_t)q + 1]) ? 0 : 1;
+            *any |= (*blk)[(size_t)q] != 0;
+        }
+    return PP_OK;
+}
+
+int star_reval_outputs(pp_ctx* c, const std::vector<uint8_t>& blk, bool any, int32_t* n_nodes) {
+    Forest& f = c->star.f;
+    const int Q = f.Q;
+    hipStream_t st = c->stream;
+    if (any) {
+        PP_HIP(f.blocked.reserve(Q));
+        PP_HIP(hipMemcpy(f.blocked.p, blk.data(), Q, hipMemcpyHostToDevice));
+    }
+    f.any_blocked = any;
+    if (n_nodes) {
+        PP_HIP(hipMemcpyAsync(n_nodes, f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+        PP_HIP(hipStreamSynchronize(st));
+    }
+    return PP_OK;
+}
+
+}  // namespace ppamd
+
+namespace {
+
+// The device pass over Q trees of hn[q] nodes in the rows tr (tree q at q * cap): *kept the nodes
+// that stay over all trees; new_index (may be null) the sum of hn entries.  blocked (host, may be
+// null): the roots that fail verify.  d_n (may be null): the trees' node counts on the device.
+// any_order with the cost / elen rows: an RRT* forest (RevalArgs), else false and null.
+// One synchronisation; on PP_ERR_STEER_OVERFLOW the trees are unmodified.
+int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t cap,
+              const std::vector<int>& hn, const uint8_t* blocked, int* d_n, int64_t* kept,
+              int32_t* new_index, bool any_order = false, double* cost = nullptr,
+              double* elen = nullptr) {
+    RevalArgs a;
+    int passes = 0, rc;
+    if ((rc = reval_setup(c, tr, Q, cap, hn, blocked, d_n, any_order, cost, elen, 0, &a, &passes)))
+        return rc;
+    PP_HIP(launch_revalidate(c->stream, sc, a, passes));
+    return reval_finish(c, a, kept, new_index);
 }
 
 // the f32 screen tolerance pp_rrt_new derives from the scene and the root
@@ -204,20 +265,10 @@ int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_
     if (!s.valid) return set_err(PP_ERR_STATE, "no RRT* batch to revalidate: pp_star_new has not been called");
     Forest& f = s.f;
     const int Q = f.Q;
-    hipStream_t st = ctx->stream;
-    std::vector<int> hn((size_t)Q);
-    std::vector<double> starts(3 * (size_t)Q);
-    PP_HIP(hipMemcpyAsync(hn.data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipMemcpyAsync(starts.data(), f.d_starts.p, starts.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
-    // the roots that fail verify in the scene as it is now (Forest::init)
-    std::vector<uint8_t> blk((size_t)Q, 0);
+    std::vector<int> hn;
+    std::vector<uint8_t> blk;
     bool any = false;
-    if (ctx->scene.polygons())
-        for (int q = 0; q < Q; ++q) {
-            blk[(size_t)q] = ctx->scene.point_ok(starts[3 * (size_t)q], starts[3 * (size_t)q + 1]) ? 0 : 1;
-            any |= blk[(size_t)q] != 0;
-        }
+    if ((rc = star_reval_inputs(ctx, &hn, &blk, &any))) return rc;
     SceneDev sc = ctx->scene_dev();  // the scene of the batch's own steer rounds (star_args)
     sc.step_size = f.step;
     int64_t kept = 0, total = 0;
@@ -227,15 +278,7 @@ int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_
     if ((rc = reval_run(ctx, sc, f.tree_dev(), Q, (size_t)f.cap, hn, any ? blk.data() : nullptr,
                         f.n.p, &kept, new_index, true, s.cost.p, s.elen.p)))
         return rc;
-    if (any) {
-        PP_HIP(f.blocked.reserve(Q));
-        PP_HIP(hipMemcpy(f.blocked.p, blk.data(), Q, hipMemcpyHostToDevice));
-    }
-    f.any_blocked = any;
-    if (n_nodes) {
-        PP_HIP(hipMemcpyAsync(n_nodes, f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-        PP_HIP(hipStreamSynchronize(st));
-    }
+    if ((rc = star_reval_outputs(ctx, blk, any, n_nodes))) return rc;
     if (n_dropped) *n_dropped = total - kept;
     return PP_OK;
 }

@@ -708,14 +708,40 @@ class RRTStarBatch:
         self.last_dropped = dropped.value
         return n, new_index[:total]
 
-    def set_space(self, space: Space):
+    def repair(self, rounds: int = 1, n_old=None):
+        """``revalidate`` with up to ``rounds`` (0..16) re-attachment rounds (pp_star_repair): a
+        dropped node whose own edge failed looks for a new parent among the star_k nearest kept
+        nodes of its tree (the edge keeps its pose, like a rewire; the first strict minimum of
+        cost[parent] + edge cost), and the subtree under it is kept again with its costs
+        recomputed; later rounds give the children of a top that found no parent their own try.
+        ``rounds = 0`` is ``revalidate``.  Returns (n_nodes, new_index) as ``revalidate`` does and
+        sets ``last_dropped``, ``last_reattached`` (tops that found a parent) and
+        ``last_recovered`` (nodes kept that ``revalidate`` would have dropped)."""
+        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
+        total = int(n_old.sum(dtype=np.int64))
+        new_index = np.zeros(max(total, 1), dtype=np.int32)
+        n = np.zeros(self.q, dtype=np.int32)
+        dropped, rea, rec = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        ip = C.POINTER(C.c_int32)
+        _ffi.check(_ffi.lib().pp_star_repair(
+            self.ctx.handle, int(rounds), n.ctypes.data_as(ip), C.byref(dropped), C.byref(rea),
+            C.byref(rec), new_index.ctypes.data_as(ip)))
+        self.last_dropped = dropped.value
+        self.last_reattached = rea.value
+        self.last_recovered = rec.value
+        return n, new_index[:total]
+
+    def set_space(self, space: Space, repair_rounds: int | None = None):
         """Replace the scene of the batch and keep every tree where it still holds: uploads
-        ``space`` into the batch's context and revalidates.  (Uploading a scene alone does not
-        stop the batch: its trees are unverified until ``revalidate``.)"""
+        ``space`` into the batch's context and revalidates — with ``repair_rounds`` given, by
+        ``repair(repair_rounds)``.  (Uploading a scene alone does not stop the batch: its trees
+        are unverified until ``revalidate``.)"""
         n_old = self.state()[0]
         space._upload(self.ctx)
         self.space = space
-        return self.revalidate(n_old)
+        if repair_rounds is None:
+            return self.revalidate(n_old)
+        return self.repair(repair_rounds, n_old)
 
     # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path, DESIGN.md §3.7)
     def plan(self, goals):
