@@ -54,37 +54,26 @@ typedef __attribute__((address_space(1))) void glb_void;
 // device-resident DevState, so the host enqueues windows back to back and synchronises once per
 // batch.
 
-constexpr int kQPL = 8;                     // samples per lane in the screen
-constexpr int kQPB = 64 * kQPL;                  // samples per screen workgroup (its waves share them)
+// (kQPL, kQPB, kScanWaves, kScanBlk, kScanGrid and the tiling itself: pp_screen_geom.h)
 constexpr int kScanThreads = 512;                // window_kernel workgroup (8 waves, 256 VGPRs)
 constexpr bool kWinRepair = true;                // repairs inside the window kernel (no spill)
-constexpr int kScanWaves = kScanThreads / 64;
-constexpr int kScanBlk = 16;             // nodes per block (one block minimum per sample)
+static_assert(kScanWaves == kScanThreads / 64, "the tiling's waves per workgroup");
+static_assert(kScreenBlocks * kQPB >= kMaxWindow, "the tiling's blocks cover a window");
+// the screen's tiling and work list for every count of sample rows, built at compile time
+__constant__ const ScreenTables kScreenTables = make_screen_tables();
 constexpr int kStage = 7936;                     // chunk nodes staged in LDS per round
-constexpr int kGrab = 64;                        // nodes a screen wave takes from the counter
 constexpr int kExactNode = 1 << 30;              // screen partial key: a node index, not a block
 // LDS of a screen workgroup: the wave merge (best, second, key per wave and sample; sample ids;
 // the samples' f32 operands), then the staged chunk
 constexpr int kScreenStageOff = (3 * kScanWaves + 3) * kQPB * 4;
-constexpr int kScanGrid = 255;           // screen workgroups per window (one per CU, with
-                                                 // the resolve workgroup: <= 256 CUs)
 
-// node chunks of the screen for a window of K samples: the nqb sample blocks x chunks workgroups
-// fill kScanGrid; every chunk is a whole number of kScanBlk blocks
+// the nearest API's node chunks for K given samples: nqb full sample blocks x chunks workgroups
+// fill kScanGrid (the window's screen is tiled by screen_geom, from the samples it screens)
 __host__ __device__ inline int scan_chunks(int K) {
     const int nqb = (K + kQPB - 1) / kQPB;
     int c = kScanGrid / nqb;
     if (c > kMaxChunks) c = kMaxChunks;
     return c < 1 ? 1 : c;
-}
-__host__ __device__ inline int scan_chunk_len(int n, int chunks) {
-    int cl = (n + chunks - 1) / chunks;
-    if (cl < kScanWaves * kScanBlk) cl = kScanWaves * kScanBlk;
-    return (cl + kScanBlk - 1) & ~(kScanBlk - 1);
-}
-__host__ __device__ inline int scan_chunks_used(int n, int chunks) {
-    const int cl = scan_chunk_len(n, chunks);
-    return (n + cl - 1) / cl;
 }
 
 struct Top2 {
@@ -132,7 +121,7 @@ struct SamplesArgs {
     float2* sxy[2];   // sorted position -> (x, y) f32 (the pair search's prefilter)
     double* ssx[2];   // sorted position -> x, y (f64): the screen's coalesced sample loads
     double* ssy[2];
-    float2* ob[2];    // [K / kQPB] the screen block's centre o (f32) of each kQPB sorted samples
+    float2* ob[2];    // [kScreenBlocks] the centre o (f32) of each screen block's sorted samples
     double* sq[2];    // sample -> |q - o|^2 about its block's centre (f64, exact)
     int* ipos[2];     // sample -> sorted position (the screen's partials are stored by position)
     const SceneDev* scp = nullptr;       // the scene in device memory (point_blocked)
@@ -168,19 +157,6 @@ __device__ inline int morton16(int x, int y) {
 // LDS of samples_role: the Morton histogram, each sample's cell, the sorted window's sample ids,
 // the count of samples in an obstacle
 constexpr int kSamplesLds = 256 * 4 + kMaxWindow + kMaxWindow * 4 + 16 + kMaxWindow;
-
-// The screen's geometry for Ws screened samples (window mode): nqb blocks of kQPB samples x
-// chunks node chunks on at most kScanGrid workgroups, nqb x chunks a multiple of 8 when it can be
-// (the XCD-aware mapping), chunks <= kMaxChunks (the partials' capacity).
-__host__ __device__ inline int screen_chunks(int Ws) {
-    const int nqb = (Ws + kQPB - 1) / kQPB;
-    if (nqb <= 0) return 1;
-    int c = kScanGrid / nqb;
-    if (c > kMaxChunks) c = kMaxChunks;
-    for (int d = c; d >= 1 && d * 4 >= c * 3; --d)
-        if (((nqb * d) & 7) == 0) return d;
-    return c < 1 ? 1 : c;
-}
 
 __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t start,
                              char* smem) {
@@ -276,10 +252,11 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
     }
     __syncthreads();
     const int Ws = W - *s_nb;  // screened samples: sorted positions [0, Ws)
-    if (tid == 0) {
-        st->Wsp[np] = Ws;
-        st->chp[np] = screen_chunks(Ws);
-    }
+    if (tid == 0) st->Wsp[np] = Ws;
+    // the screen's blocks of rows for Ws samples (the tiling's split; its chunks are the
+    // screen's and nn_finalize's business)
+    const int R = screen_rows(Ws), nqb = (R + kQPL - 1) / kQPL;
+    const int rbase = nqb ? R / nqb : 0, rextra = R - rbase * nqb;  // (screen_geom's row split)
     if (tid < 64) {  // exclusive prefix of the 256 cell counts, 4 per lane
         int v[4], sum = 0;
 #pragma unroll
@@ -314,7 +291,7 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
         s_j[bk ? base + (int)__popcll(mb & ((1ull << (tid & 63)) - 1)) : atomicAdd(&s_hist[s_cell[j]], 1)] = j;
     }
     __syncthreads();
-    // the screen's blocks of kQPB sorted samples, one wave each: the sorted window (coalesced; the
+    // the screen's blocks of sorted samples (rows of 64, split as the tiling's): the sorted window (coalesced; the
     // coordinates drawn again from the stream, bit-identical), the centre o of the block's
     // bounding box (f32) and every sample's |q - o|^2 in f64 — (q - o) rounded to f32 per axis,
     // the screen's own operands, squared exactly (nn_finalize adds it back to the screen values)
@@ -331,13 +308,15 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
     // gave each block to one wave, 8 samples per lane, and 16 waves shared 4-8 blocks: the
     // sampling workgroup was nn_finalize's long pole, ~30 of its 27-30 us)
     // s_bb: [kMaxWindow / 64][4] wave boxes (x0, x1, y0, y1), then [kMaxWindow / kQPB][2] block
-    // centres — over s_hist and the head of s_cell, both dead after the scatter
+    // centres, then [kMaxWindow / 64] each row's block — over s_hist and the head of s_cell, both
+    // dead after the scatter
     float* s_bb = reinterpret_cast<float*>(s_hist);
+    int* s_rb = reinterpret_cast<int*>(s_bb + 4 * (kMaxWindow / 64) + 2 * (kMaxWindow / kQPB));  // [rows]
     (void)wv;
     __syncthreads();  // (s_hist's last readers: the scatter above)
     constexpr int kMaxK = 4;  // positions per thread: both callers run 1024 threads
     static_assert(kMaxWindow <= 1024 * kMaxK, "samples_role: positions per thread");
-    static_assert((4 * (kMaxWindow / 64) + 2 * (kMaxWindow / kQPB)) * 4 <= 256 * 4 + kMaxWindow,
+    static_assert((5 * (kMaxWindow / 64) + 2 * (kMaxWindow / kQPB)) * 4 <= 256 * 4 + kMaxWindow,
                   "samples_role: the box slots fit s_hist and s_cell");
     double xs[kMaxK], ys[kMaxK];
 #pragma unroll
@@ -372,10 +351,11 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
         if (NT * (k + 1) >= kMaxWindow) break;
     }
     __syncthreads();
-    const int nqb = (Ws + kQPB - 1) / kQPB;
     if (tid < nqb) {  // block tid's centre: the middle of its samples' box (f32)
         float x0 = __builtin_inff(), x1 = -__builtin_inff(), y0 = __builtin_inff(), y1 = -__builtin_inff();
-        for (int w = tid * (kQPB / 64); w < (tid + 1) * (kQPB / 64) && w * 64 < Ws; ++w) {
+        const int w0 = screen_split_row0(rbase, rextra, tid), w1 = screen_split_row0(rbase, rextra, tid + 1);
+        for (int w = w0; w < w1 && w * 64 < Ws; ++w) {
+            s_rb[w] = tid;  // (row -> block, for the |q - o|^2 pass)
             const float* b = s_bb + 4 * w;
             x0 = fminf(x0, b[0]);
             x1 = fmaxf(x1, b[1]);
@@ -393,7 +373,7 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
     for (int k = 0; k < kMaxK; ++k) {
         const int pos = tid + k * NT;
         if (pos < Ws) {
-            const int qb = pos / kQPB;
+            const int qb = s_rb[pos >> 6];
             const float oxf = s_bb[4 * (kMaxWindow / 64) + 2 * qb];
             const float oyf = s_bb[4 * (kMaxWindow / 64) + 2 * qb + 1];
             const float qpx = (float)(xs[k] - (double)oxf), qpy = (float)(ys[k] - (double)oyf);
@@ -468,12 +448,19 @@ struct WinKArgs {
 // The screen's winner re-evaluation of a block no longer in LDS (trees past one staging round):
 // the block's 16 nodes from global memory with the screen's own prep and arithmetic, the lowest
 // u with value == best and the minimum of the others.  Out of line: inlined, the compiler merges
-// it with the LDS path into flat loads.
+// it with the LDS path into flat loads.  The result comes back by value, in registers: passed by
+// reference, ui and other lived in scratch, 8 bytes stored and reloaded by every sample's thread.
+struct BlockPick {
+    int ui;       // the lowest node of the block with value == best (-1: none)
+    float other;  // the minimum of the block's other nodes
+};
 template <bool kExp, int kNodes = kScanBlk>
-__device__ __attribute__((noinline)) void screen_block_global(const float* __restrict__ bx,
-                                                              const float* __restrict__ by, float qx,
-                                                              float qy, float oxf, float oyf,
-                                                              float best, int& ui, float& other) {
+__device__ __attribute__((noinline)) BlockPick screen_block_global(const float* __restrict__ bx,
+                                                                   const float* __restrict__ by,
+                                                                   float qx, float qy, float oxf,
+                                                                   float oyf, float best) {
+    int ui = -1;
+    float other = __builtin_inff();
     for (int u = 0; u < kNodes; ++u) {
         float px = bx[u], py = by[u], pw = 0.0f;
         if (kExp) {
@@ -488,27 +475,39 @@ __device__ __attribute__((noinline)) void screen_block_global(const float* __res
         else
             other = __builtin_fminf(other, d);
     }
+    return BlockPick{ui, other};
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <bool kExp>
-__device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& a, int b,
-                                                               char* smem) {
-    DevState* st = a.st;
+// A block of kScanBlk staged nodes in registers: x | y | |n-o|^2, read as broadcast ds_read_b128.
+struct NodeBlk {
+    float4 vx[kScanBlk / 4], vy[kScanBlk / 4], vw[kScanBlk / 4];
+    __device__ __forceinline__ void load(const float* stg, int u0) {
+#pragma unroll
+        for (int v = 0; v < kScanBlk / 4; ++v) {
+            vx[v] = *reinterpret_cast<const float4*>(stg + u0 + 4 * v);
+            vy[v] = *reinterpret_cast<const float4*>(stg + kStage + u0 + 4 * v);
+            vw[v] = *reinterpret_cast<const float4*>(stg + 2 * kStage + u0 + 4 * v);
+        }
+    }
+    static __device__ __forceinline__ float at(const float4& q, int i) {
+        return i == 0 ? q.x : i == 1 ? q.y : i == 2 ? q.z : q.w;
+    }
+    __device__ __forceinline__ float x(int u) const { return at(vx[u >> 2], u & 3); }
+    __device__ __forceinline__ float y(int u) const { return at(vy[u >> 2], u & 3); }
+    __device__ __forceinline__ float w(int u) const { return at(vw[u >> 2], u & 3); }
+};
+
+// One screen workgroup: sample block qb (kR rows of 64 sorted positions from row0: kR samples per
+// lane, none padded) against chunk c of the `chunks` the block splits the ns nodes into.
+template <bool kExp, int kR>
+__device__ __attribute__((always_inline)) inline void scan_tile(const WinKArgs& a, char* smem,
+                                                               int qb, int row0, int c, int chunks,
+                                                               int W, int ns) {
+    static_assert(kR >= 1 && kR <= kQPL, "rows of a sample block");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // window mode: the samples not in an obstacle (sorted first) on the geometry samples_role
-    // chose for them; the nearest API: the given samples on the launch's geometry
-    const int W = kExp ? st->Wsp[a.p] : st->Wp[a.p];
-    const int ns = st->n_scan;
-    if (b == 0 && tid == 0) st->nsp[a.p] = ns;
-    const int chunks = kExp ? st->chp[a.p] : a.chunks;
-    const int nqb = kExp ? (W + kQPB - 1) / kQPB : a.nqb;
-    const int G = nqb * chunks;
-    if (b >= G) return;
-    const int t = (G & 7) == 0 ? (b & 7) * (G >> 3) + (b >> 3) : b;
-    const int qb = t % nqb, c = t / nqb;
-    const int qbase = qb * kQPB;
+    const int qbase = row0 * 64;
     if (qbase >= W) return;
     const int cl = scan_chunk_len(ns, chunks);
     const int c0 = c * cl;
@@ -520,12 +519,12 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
     // round up to ~250k tree nodes at K = 4096): LDS-DMA (global_load_lds_dwordx4, lane l brings
     // nodes 4l..4l+3 of a 256-node quarter, no registers) issued before the samples are read, so
     // the two latencies overlap; each thread then preps its own float4s in place — (n - o,
-    // |n - o|^2) in the expanded form, each node once instead of once per lane.  The waves take
-    // kGrab-node pieces from an LDS counter (no wave idles at the merge barrier while another
-    // still screens); a wave's pieces come in increasing order, so its first block to reach the
-    // best is its lowest.  The block loop reads its 16 nodes as broadcast ds_read_b128.
+    // |n - o|^2) in the expanded form, each node once instead of once per lane.  The waves split
+    // the round's blocks evenly, each a contiguous run in increasing order, so a wave's first block
+    // to reach the best is its lowest.  (Until the balanced tiling the waves took 64-node pieces
+    // from an LDS counter: a workgroup's time came in steps of 8 waves x 64 nodes, which ate the
+    // tiling's gain.)  The block loop reads its 16 nodes as broadcast ds_read_b128.
     float* stg = reinterpret_cast<float*>(smem + kScreenStageOff);
-    int* s_next = reinterpret_cast<int*>(stg + 3 * kStage);
     auto issue_round = [&](int r0) {
         const int len = min(kStage, L - r0);
         for (int q4 = wave; q4 * 256 < len; q4 += kScanWaves) {
@@ -537,8 +536,8 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
         }
     };
     issue_round(0);
-    float qxr[kQPL], qyr[kQPL], best[kQPL], second[kQPL];
-    int sid[kQPL], blk[kQPL], bi[kQPL];
+    float qxr[kR], qyr[kR], best[kR], second[kR];
+    int sid[kR], blk[kR], bi[kR];
     float oxf = 0.0f, oyf = 0.0f;
     if (kExp) {
         // window mode: samples_role left the window sorted (f64, coalesced), each screen block's
@@ -547,7 +546,7 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
         oxf = o.x;
         oyf = o.y;
 #pragma unroll
-        for (int r = 0; r < kQPL; ++r) {
+        for (int r = 0; r < kR; ++r) {
             const int pos = qbase + r * 64 + lane;
             const bool in = pos < W;
             sid[r] = in ? a.perm[a.p][pos] : -1;
@@ -561,7 +560,7 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
         const double* qxs = a.wsx[a.p];
         const double* qys = a.wsy[a.p];
 #pragma unroll
-        for (int r = 0; r < kQPL; ++r) {
+        for (int r = 0; r < kR; ++r) {
             const int pos = qbase + r * 64 + lane;
             sid[r] = pos < W ? pos : -1;
             qxr[r] = sid[r] >= 0 ? (float)qxs[pos] : 0.0f;
@@ -569,7 +568,7 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
         }
     }
 #pragma unroll
-    for (int r = 0; r < kQPL; ++r) {
+    for (int r = 0; r < kR; ++r) {
         best[r] = __builtin_inff();
         second[r] = __builtin_inff();
         blk[r] = -1;
@@ -579,7 +578,7 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
         float* s_qx = reinterpret_cast<float*>(smem) + (3 * kScanWaves + 1) * kQPB;
         if (wave == 0) {
 #pragma unroll
-            for (int r = 0; r < kQPL; ++r) {
+            for (int r = 0; r < kR; ++r) {
                 s_qx[r * 64 + lane] = qxr[r];
                 s_qx[kQPB + r * 64 + lane] = qyr[r];
             }
@@ -599,10 +598,52 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
             pw = 0.0f;
         }
     };
+    // One block of kScanBlk nodes (in registers) against the lane's samples: each sample's block
+    // minimum, merged into (best, second, block).  Expanded form: two nodes per packed FMA
+    // (v_pk_fma_f32: each half the exactly rounded fmaf of the scalar form, so the winner
+    // re-evaluation below stays bit-identical), the pair folded in by one v_min3 per sample,
+    // min(min(bm, d.x), d.y) — 8 three-input minima per sample and block (written as
+    // min(bm, min(d.x, d.y)) it compiled to 12).  The compiler issues the block's inner FMAs
+    // first, then the outer ones; pinning the order per node pair with scheduling barriers and
+    // reading block u + 1 ahead into a second register set measured slower.
+    auto block = [&](const NodeBlk& nb, int k) {
+        float bm[kR];
+        if (kExp) {
+#pragma unroll
+            for (int u = 0; u < kScanBlk; u += 2) {
+                const f32x2 PX = {nb.x(u), nb.x(u + 1)}, PY = {nb.y(u), nb.y(u + 1)};
+                const f32x2 PW = {nb.w(u), nb.w(u + 1)};
+#pragma unroll
+                for (int r = 0; r < kR; ++r) {
+                    const f32x2 QX = {qxr[r], qxr[r]}, QY = {qyr[r], qyr[r]};
+                    const f32x2 d = __builtin_elementwise_fma(
+                        QX, PX, __builtin_elementwise_fma(QY, PY, PW));
+                    bm[r] = u == 0 ? __builtin_fminf(d.x, d.y)
+                                   : __builtin_fminf(__builtin_fminf(bm[r], d.x), d.y);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < kScanBlk; ++u) {
+#pragma unroll
+                for (int r = 0; r < kR; ++r) {
+                    const float d = val(r, nb.x(u), nb.y(u), nb.w(u));
+                    bm[r] = u == 0 ? d : __builtin_fminf(bm[r], d);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kR; ++r) {
+            second[r] = __builtin_amdgcn_fmed3f(best[r], bm[r], second[r]);
+            if (bm[r] < best[r]) {
+                best[r] = bm[r];
+                blk[r] = k;
+            }
+        }
+    };
     int r0 = 0;
     for (;;) {
         const int len = min(kStage, L - r0);
-        if (tid == 0) *s_next = 0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA has landed
         __syncthreads();                                   // ... and every other wave's
         for (int i = 4 * tid; i < len; i += 4 * kScanThreads) {  // prep in place
@@ -618,66 +659,24 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
             *reinterpret_cast<float4*>(stg + 2 * kStage + i) = w4;
         }
         __syncthreads();
-        for (;;) {
-            int g0 = 0;
-            if (lane == 0) g0 = atomicAdd(s_next, kGrab);
-            g0 = __builtin_amdgcn_readfirstlane(__shfl(g0, 0));
-            if (g0 >= len) break;
-            const int g1 = min(g0 + kGrab, len);
-            const int gb = g0 + ((g1 - g0) & ~(kScanBlk - 1));  // whole blocks (a tail: the last)
+        {
+            // the round's whole blocks split evenly over the waves, each a contiguous run (at
+            // most one block apart); the tail (< kScanBlk nodes, the chunk's last) is the last
+            // wave's
+            const int nblk = len / kScanBlk;
+            const int wv = __builtin_amdgcn_readfirstlane(wave);  // (scalar loop bounds)
+            const int g0 = (wv * nblk / kScanWaves) * kScanBlk;
+            const int gb = ((wv + 1) * nblk / kScanWaves) * kScanBlk;
+            const int g1 = wv == kScanWaves - 1 ? len : gb;
             for (int u0 = g0; u0 < gb; u0 += kScanBlk) {
-                float px[kScanBlk], py[kScanBlk], pw[kScanBlk];
-#pragma unroll
-                for (int v = 0; v < kScanBlk / 4; ++v) {
-                    const float4 ax = *reinterpret_cast<const float4*>(stg + u0 + 4 * v);
-                    const float4 ay = *reinterpret_cast<const float4*>(stg + kStage + u0 + 4 * v);
-                    const float4 aw = *reinterpret_cast<const float4*>(stg + 2 * kStage + u0 + 4 * v);
-                    px[4 * v] = ax.x, px[4 * v + 1] = ax.y, px[4 * v + 2] = ax.z, px[4 * v + 3] = ax.w;
-                    py[4 * v] = ay.x, py[4 * v + 1] = ay.y, py[4 * v + 2] = ay.z, py[4 * v + 3] = ay.w;
-                    pw[4 * v] = aw.x, pw[4 * v + 1] = aw.y, pw[4 * v + 2] = aw.z, pw[4 * v + 3] = aw.w;
-                }
-                float bm[kQPL];
-                if (kExp) {
-                    // two nodes per packed FMA (v_pk_fma_f32: each half the exactly rounded
-                    // fmaf of the scalar form, so the winner re-evaluation below stays
-                    // bit-identical), the pair's minimum folded in by one v_min3
-#pragma unroll
-                    for (int u = 0; u < kScanBlk; u += 2) {
-                        const f32x2 PX = {px[u], px[u + 1]}, PY = {py[u], py[u + 1]};
-                        const f32x2 PW = {pw[u], pw[u + 1]};
-#pragma unroll
-                        for (int r = 0; r < kQPL; ++r) {
-                            const f32x2 QX = {qxr[r], qxr[r]}, QY = {qyr[r], qyr[r]};
-                            const f32x2 d = __builtin_elementwise_fma(
-                                QX, PX, __builtin_elementwise_fma(QY, PY, PW));
-                            const float m = __builtin_fminf(d.x, d.y);
-                            bm[r] = u == 0 ? m : __builtin_fminf(bm[r], m);
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < kScanBlk; ++u) {
-#pragma unroll
-                        for (int r = 0; r < kQPL; ++r) {
-                            const float d = val(r, px[u], py[u], pw[u]);
-                            bm[r] = u == 0 ? d : __builtin_fminf(bm[r], d);
-                        }
-                    }
-                }
-                const int k = c0 + r0 + u0;
-#pragma unroll
-                for (int r = 0; r < kQPL; ++r) {
-                    second[r] = __builtin_amdgcn_fmed3f(best[r], bm[r], second[r]);
-                    if (bm[r] < best[r]) {
-                        best[r] = bm[r];
-                        blk[r] = k;
-                    }
-                }
+                NodeBlk nb;
+                nb.load(stg, u0);
+                block(nb, c0 + r0 + u0);
             }
             for (int u = gb; u < g1; ++u) {  // the chunk's tail (< kScanBlk nodes): exact top-2
                 const float px = stg[u], py = stg[kStage + u], pw = stg[2 * kStage + u];
 #pragma unroll
-                for (int r = 0; r < kQPL; ++r) {
+                for (int r = 0; r < kR; ++r) {
                     const float d = val(r, px, py, pw);
                     second[r] = __builtin_amdgcn_fmed3f(best[r], d, second[r]);
                     if (d < best[r]) {
@@ -705,7 +704,7 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
     int* s_i = reinterpret_cast<int*>(s_s + kScanWaves * kQPB);
     int* s_sid = s_i + kScanWaves * kQPB;                      // [kQPB]
 #pragma unroll
-    for (int r = 0; r < kQPL; ++r) {
+    for (int r = 0; r < kR; ++r) {
         s_b[wave * kQPB + r * 64 + lane] = best[r];
         s_s[wave * kQPB + r * 64 + lane] = second[r];
         s_i[wave * kQPB + r * 64 + lane] =
@@ -713,7 +712,7 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
         if (wave == 0) s_sid[r * 64 + lane] = sid[r];
     }
     __syncthreads();
-    if (tid < kQPB) {  // one thread per sample (sorted position qbase + tid)
+    if (tid < 64 * kR) {  // one thread per sample (sorted position qbase + tid)
         float bb = s_b[tid], ss = s_s[tid];
         int key = s_i[tid];
 #pragma unroll
@@ -755,7 +754,9 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
                         other = __builtin_fminf(other, d);
                 }
             } else {
-                screen_block_global<kExp>(nx + key, ny + key, qx, qy, oxf, oyf, bb, ui, other);
+                const BlockPick g = screen_block_global<kExp>(nx + key, ny + key, qx, qy, oxf, oyf, bb);
+                ui = g.ui;
+                other = g.other;
             }
             idx = key + ui;
             ss = __builtin_fminf(ss, other);
@@ -766,6 +767,41 @@ __device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& 
             a.psecond[o] = ss;
             a.pidx[o] = idx;
         }
+    }
+}
+
+// Screen workgroup b: its tile, and the tile's loop with as many accumulators as the block has rows.
+// Window mode: the tiling for the samples not in an obstacle (samples_role sorted them first) —
+// workgroup b takes its XCD's share of the work list, so the workgroups that stream one node range
+// share an L2.  The nearest API: the given samples in full blocks on the launch's geometry.
+template <bool kExp>
+__device__ __attribute__((always_inline)) inline void scan_role(const WinKArgs& a, int b,
+                                                               char* smem) {
+    DevState* st = a.st;
+    const int ns = st->n_scan;
+    if (b == 0 && threadIdx.x == 0) st->nsp[a.p] = ns;
+    if constexpr (kExp) {
+        const int W = st->Wsp[a.p];
+        const ScreenWork w = screen_work_unpack(kScreenTables.wg[screen_rows(W)][b]);  // (one load)
+        if (w.rows == 0) return;  // no tile for this workgroup
+        const int qb = w.k, c = w.c, row0 = w.row0, chunks = w.chunks;
+        switch (w.rows) {  // (uniform over the workgroup)
+            case 1: scan_tile<kExp, 1>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 2: scan_tile<kExp, 2>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 3: scan_tile<kExp, 3>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 4: scan_tile<kExp, 4>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 5: scan_tile<kExp, 5>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 6: scan_tile<kExp, 6>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 7: scan_tile<kExp, 7>(a, smem, qb, row0, c, chunks, W, ns); break;
+            case 8: scan_tile<kExp, 8>(a, smem, qb, row0, c, chunks, W, ns); break;
+            default: break;
+        }
+    } else {
+        const int G = a.nqb * a.chunks;
+        if (b >= G) return;
+        const int t = (G & 7) == 0 ? (b & 7) * (G >> 3) + (b >> 3) : b;
+        const int qb = t % a.nqb, c = t / a.nqb;
+        scan_tile<kExp, kQPL>(a, smem, qb, qb * kQPL, c, a.chunks, st->Wp[a.p], ns);
     }
 }
 
@@ -876,6 +912,9 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
     __shared__ double s_rd[kFinWaves];
     __shared__ int s_ri[kFinWaves];
     __shared__ float2 s_dn[kFinDelta];   // nodes appended after the screen's snapshot (f32)
+    // per row of 64 sorted positions: the chunks its samples' partials fill and their length (one
+    // wave works them out for the workgroup: a block lookup and two divisions a row, not a wave)
+    __shared__ int s_nch[kMaxWindow / 64], s_cl[kMaxWindow / 64];
     FS(0)
     const bool voided = st->void_seq == seq || st->error;
     if (gen_next && blockIdx.x == gridDim.x - 1) {
@@ -892,7 +931,6 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
     }
     const int W = voided ? 0 : st->Wp[p];
     const int ns = st->nsp[p], n = st->n;
-    const int chunks = cand ? st->chp[p] : chunks_api;  // window mode: samples_role's geometry
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         st->W = W;
         st->n_scan = n;
@@ -909,24 +947,37 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
     const bool in = q < W && !qblk;
     const int D = n - ns, Dl = min(D, kFinDelta);  // appended nodes (staged: the first kFinDelta)
     for (int k = tid; k < Dl; k += kFinThreads) s_dn[k] = make_float2(x32[ns + k], y32[ns + k]);
+    if (tid < kMaxWindow / 64) {
+        // the node chunks of the samples in row tid — window mode: those of the row's block in the
+        // tiling for the window's screened samples; the nearest API: the launch's
+        const int chunks = cand ? screen_chunks_of_row(kScreenTables.g[screen_rows(st->Wsp[p])], tid)
+                                : chunks_api;
+        const int cl = scan_chunk_len(ns, chunks);
+        s_cl[tid] = cl;
+        s_nch[tid] = (ns + cl - 1) / cl;
+    }
     if (tid < kFinSamples) s_pc[tid] = 0;
     if (tid == 0) s_fmask = 0;
     __syncthreads();
     FS(1)
     // ---- 1. the sample's nearest node
     if (in) {
-        const int n_chunks = scan_chunks_used(ns, chunks);
+        const int pq = ipos ? ipos[q] : q;  // the sample's sorted position (the partials' index)
         Top2 t{__builtin_inff(), __builtin_inff(), -1};
         const double qq = sq ? sq[q] : 0.0;  // window mode: screen values are d2 - |q - o|^2
-        float cb = __builtin_inff(), cs = __builtin_inff();  // this lane's chunk: raw screen top-2
-        int ci = -1;
-        const int pq = ipos ? ipos[q] : q;  // the sample's sorted position (the partials' index)
+        // this lane's chunk: raw screen top-2.  Every lane loads (the partials hold kMaxChunks
+        // chunks per sample) and the lanes past the sample's chunks drop what they read: the
+        // chunk count hangs on the sample's position and the loads do not wait for it.
+        static_assert(kMaxChunks == 64, "one lane per chunk");
+        const size_t po = (size_t)lane * stride + pq;
+        float cb = pbest[po], cs = psecond[po];
+        int ci = pidx[po];
+        const int n_chunks = s_nch[pq >> 6];
         if (lane < n_chunks) {
-            const size_t o = (size_t)lane * stride + pq;
-            cb = pbest[o];
-            cs = psecond[o];
-            ci = pidx[o];
             t = Top2{(float)((double)cb + qq), (float)((double)cs + qq), ci};
+        } else {
+            cb = cs = __builtin_inff();
+            ci = -1;
         }
         FSW(2)
         const double xq = qx[q], yq = qy[q];
@@ -1040,15 +1091,15 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
         const int w = (int)__builtin_ctz(fm);
         const int qf = q0 + w;
         const double cthr = s_fd[w];
-        const int n_chunks = scan_chunks_used(ns, chunks);
+        const int pf = ipos ? ipos[qf] : qf;
+        const int n_chunks = s_nch[pf >> 6];  // (uniform: every wave works on sample qf)
         if (wave == 0) {
-            const int pf = ipos ? ipos[qf] : qf;
             const bool cc = lane < n_chunks && !((double)pbest[(size_t)lane * stride + pf] > cthr);
             const uint64_t cm = __ballot(cc);
             if (lane == 0) s_cmask = cm;
         }
         __syncthreads();
-        const int cl = scan_chunk_len(ns, chunks);
+        const int cl = s_cl[pf >> 6];
         const double xq = qx[qf], yq = qy[qf];
         double bd = __builtin_inf();
         int bi = 0x7fffffff;
@@ -1604,8 +1655,8 @@ static_assert(kWinLds <= 160 * 1024, "window kernel LDS");
 static_assert((int)((3 * kScanWaves + 1) * kQPB * 4) <= kWinLds, "screen merge fits the LDS image");
 static_assert(kSamplesLds <= kWinLds, "samples_role fits the window kernel's LDS image");
 static_assert(kScreenStageOff % 16 == 0 && kScreenStageOff + 3 * kStage * 4 + 16 <= kWinLds,
-              "screen staging (x, y, |n-o|^2 of kStage nodes + the piece counter) fits");
-static_assert(kStage % 256 == 0 && kGrab % kScanBlk == 0, "whole DMA quarters and blocks");
+              "screen staging (x, y, |n-o|^2 of kStage nodes) fits");
+static_assert(kStage % 256 == 0, "whole DMA quarters");
 
 
 __global__ __launch_bounds__(kScanThreads) void window_kernel(WinKArgs a) {

@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>  // uint4
 
+#include "pp_screen_geom.h"  // kMaxChunks
+
 namespace ppamd {
 
 // dubins_literal return codes
@@ -19,7 +21,6 @@ enum : int {
 };
 
 constexpr int kCandCap = 16;         // in-window nearer-sample entries kept per sample
-constexpr int kMaxChunks = 64;       // node chunks of the NN screen (partials per sample)
 constexpr int kLiteralCap = 16384;   // points per literal-path scratch buffer
 constexpr int kLiteralWaves = 256;   // literal scratch buffers (explicit-task kernel)
 constexpr int kResolveThreads = 512;  // resolve_tail_kernel (8 waves, 256 VGPRs: the repair path)
@@ -128,7 +129,8 @@ struct DevState {
     int nsp[2];      // per parity: tree nodes its scan covered
     int Wsp[2];      // per parity: samples the screen covers (the window's samples not in an
                      // obstacle: sorted positions [0, Wsp); samples_role)
-    int chp[2];      // per parity: the screen's node chunks for those samples
+                     // — and with them the screen's tiling (pp_screen_geom.h: a table by their
+                     // rows of 64)
     int64_t void_seq;  // window sequence number voided by a truncated predecessor (-1: none)
     int resolve_bail;  // the window kernel's resolve needed a repair: resolve_tail_kernel redoes it
     int kdyn;          // adaptive window: samples drawn per window (<= K; the commit adapts it)
