@@ -835,6 +835,9 @@ constexpr int kFinThreads = 1024;
 constexpr int kFinWaves = kFinThreads / 64;
 constexpr int kFinSamples = kFinWaves;  // one wave per sample
 constexpr int kFinDelta = 4096;         // appended nodes staged in LDS (beyond: global loads)
+// eps_coord (mx 2^-23) up to which the expanded screen's first-order coordinate term stands alone:
+// mx = 2^12, past every scene whose fast-path rate is on record (their margin is unchanged)
+constexpr double kEpsCoordNear = 0x1p-11;
 
 // The window's samples binned by Morton cell (samples_role): the pair search's spatial index.
 struct PairGrid {
@@ -1002,12 +1005,24 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
                 }
             } else {  // expanded screen: rounding of |n-o|^2 - 2(q-o).(n-o) about the block centre
                 const double qn = sqrt(qq);
-                const double D = (t.s < __builtin_inff() ? sqrt((double)t.s) : D1) + 1.0;
+                double D = (t.s < __builtin_inff() ? sqrt((double)t.s) : D1) + 1.0;
                 // |dE| <= 5u (|n-o|^2 + 2|q-o||n-o|) for the f32 inputs and arithmetic
                 // (u = 2^-24, |n-o| <= |q-o| + D for the winner and the runner-up), plus the f32
-                // rounding of the node coordinates (|dn| <= eps_coord / 2 per axis)
+                // rounding of the node coordinates (|dn| <= eps_coord / 2 per axis): a node at
+                // the true distance d screens at d^2 + 2 dn.(n - q) + |dn|^2, |dn| < eps_coord.
+                // The first-order term 8 eps_coord (D + 1) also covers |dn|^2 and the error of D
+                // itself (read off the screen's own values) while eps_coord is far below 1 (it
+                // holds to about eps_coord = 0.5); a frame whose f32 ulp is no longer small
+                // against the node spacing needs both spelled out (d <= sqrt(s) + 2.5 eps_coord
+                // for a screen value s), or two nodes in different f32 cells pass for told apart
+                // (NaN from a negative t.s flags the sample: every comparison below fails)
+                double e2 = 0.0;
+                if (eps_coord > kEpsCoordNear) {
+                    D += 2.5 * eps_coord;
+                    e2 = eps_coord * eps_coord;
+                }
                 const double E = 4.0e-7 * ((qn + D) * (qn + D) + 2.0 * qn * (qn + D)) +
-                                 8.0 * eps_coord * (D + 1.0);
+                                 8.0 * eps_coord * (D + 1.0) + e2;
                 cthr = (double)t.b + 2.0 * E - qq;
                 if (t.s < __builtin_inff()) flag = !((double)t.s - (double)t.b > 2.0 * E);
             }
