@@ -40,7 +40,9 @@ extern "C" {
  * 5 (+): pp_star_revalidate added (the RRT* batch's trees kept across a scene change), nothing
  *    else changed
  * 5 (+): pp_star_repair added (dropped subtrees re-attached under kept nodes after a scene
- *    change), nothing else changed */
+ *    change), nothing else changed
+ * 5 (+): PP_COORD_MAX, pp_coord_check and pp_sincos_small_batch added; positions above
+ *    PP_COORD_MAX are now PP_ERR_INVALID_ARGUMENT, nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -51,6 +53,20 @@ extern "C" {
 #define PP_ERR_STATE (-5)          /* no scene / no planner configured yet */
 #define PP_ERR_STEER_OVERFLOW (-6) /* generate_local_course would index past n_point (panic) */
 #define PP_ERR_REFERENCE_PANIC (-7) /* finalize: an edge with no feasible Dubins word (panic) */
+
+/* The largest |x| or |y| any entry point accepts for a position (bounds, discs, polygon and grid
+ * corners, starts, goals, samples, tree nodes, query points, candidates, polyline vertices, Dubins
+ * end points): 2^61.  The nearest-node screen works in f32 first, and this is the largest power of
+ * two at which each of its intermediates stays finite: (float)q, the squared distance
+ * (qx - nx)^2 + (qy - ny)^2 <= 8 c^2 and the expanded form |n - o|^2 - 2 (q - o).(n - o)
+ * <= 24 c^2 about a block centre o, for |coordinates| <= c, against FLT_MAX < 2^128 (an infinite
+ * screen value would tie every node and hide the nearest).  A larger or non-finite position is
+ * refused on the host with PP_ERR_INVALID_ARGUMENT before anything is launched.  Inside the limit
+ * positions need not lie in the scene's bounds: the f32 margins are widened by the magnitude of
+ * the caller's points, and the answer is the sequential specification's (exact f64 nearest node,
+ * lowest index on an exact tie of dx*dx + dy*dy; verify rejects a point outside the bounds).
+ * Parity with that specification is tested up to 2^30. */
+#define PP_COORD_MAX 2305843009213693952.0 /* 2^61 */
 
 typedef struct pp_ctx pp_ctx;
 
@@ -118,6 +134,10 @@ int pp_device_count(int* n);
 int pp_create(int device, pp_ctx** out);
 int pp_destroy(pp_ctx* ctx);
 int pp_synchronize(pp_ctx* ctx);
+/* the position check every entry point applies (host only, no context): PP_OK when x[i] and y[i],
+ * i < n, are all finite and at most PP_COORD_MAX in magnitude (either array may be NULL), else
+ * PP_ERR_INVALID_ARGUMENT */
+int pp_coord_check(const double* x, const double* y, int64_t n);
 
 /* ------------------------------------------------------------- seeded sampling (host) */
 /* SplitMix64 output `ctr` of stream `seed`: the build's replacement for rand::thread_rng
@@ -149,6 +169,13 @@ int pp_dubins_path_planning_from_origin_batch(pp_ctx* ctx, const double* conf5, 
  * tpq[18 i + 3 w + {0, 1, 2}] = (t, p, q) of word w in ALL_PLANNERS order (dubins.rs:291),
  * ok[6 i + w] = 0 where the word is None (then its t, p, q are 0). */
 int pp_dubins_words_batch(pp_ctx* ctx, const double* abd, int n, double* tpq, int32_t* ok);
+/* The arc points' sine and cosine, for tests: s[i], c[i] = the library's own routine (the steer
+ * walk's, on the constants the library ships) and s_ocml[i], c_ocml[i] = the HIP math library's
+ * sincos of x[i] from the same compilation unit and flags, n arguments with |x[i]| < 2^30 (the
+ * routine's range; PP_ERR_INVALID_ARGUMENT otherwise).  The two pairs must be equal bit for bit:
+ * the walk's points are specified by the second and computed by the first. */
+int pp_sincos_small_batch(pp_ctx* ctx, const double* x, int n, double* s, double* c,
+                          double* s_ocml, double* c_ocml);
 
 /* ------------------------------------------------------------------ scene (src/rrt.rs) */
 /* create_circle(center, radius) (rrt.rs:43-60): the crate's polygon, n = ceil(2 pi r) chords and
@@ -285,7 +312,12 @@ int pp_rrt_optimize(pp_ctx* ctx, int32_t node, int i, int32_t* chain, int* n_cha
  * optimize succeeds, rrt.rs:494-498), then every edge's Dubins points, reversed.  The line is
  * returned whether or not it verifies; *verified (may be NULL) = Space::verify of it (what
  * check_finish adds).  *n = its points (cap 0 or x/y NULL: the size only); a None steer on the
- * chain returns PP_ERR_REFERENCE_PANIC (rrt.rs:529). */
+ * chain returns PP_ERR_REFERENCE_PANIC (rrt.rs:529).  The line is assembled in a fixed device
+ * buffer of 65536 points (a goal some 5000 turn radii from its parent at step 0.1).  A longer
+ * line that does not verify — a goal far outside the scene — is still answered: *n is its exact
+ * point count (counted on the device without storing it, edges of up to 2e9 steps) and
+ * *verified = 0, PP_OK for the size-only call; asking for its points is PP_ERR_CAPACITY.  A longer
+ * line that verifies is PP_ERR_CAPACITY (its length is part of the answer). */
 int pp_rrt_finalize(pp_ctx* ctx, double gx, double gy, double gyaw, int32_t parent, double* x,
                     double* y, int64_t cap, int64_t* n, uint8_t* verified);
 /* RRT::plan (rrt.rs:599-619), sequential spec: n_iter plan_one iterations (extend + check_finish

@@ -400,6 +400,8 @@ int pp_batch_new(pp_ctx* ctx, int q, const double* starts, const double* goals,
     if (q <= 0 || !starts || !seeds || max_iter < 0 || max_iter > 0x7ffffff0 || !(step_size > 0.0))
         return set_err(PP_ERR_INVALID_ARGUMENT, "bad batch arguments");
     if ((int64_t)q * (max_iter + 1) > ((int64_t)1 << 34)) return set_err(PP_ERR_CAPACITY, "batch too large");
+    for (const double* v : {starts, starts + 1, goals, goals ? goals + 1 : nullptr})
+        if ((r = check_coords(v, q, 3, "starts and goals"))) return r;
     Batch& b = ctx->batch;
     b.valid = false;
     b.stale = false;
@@ -539,6 +541,8 @@ int pp_star_new(pp_ctx* ctx, int q, const double* starts, const uint64_t* seeds,
     const int64_t cap64 = max_iter + 1;
     if ((int64_t)q * cap64 > ((int64_t)1 << 34) || (int64_t)q * kStarKMax > 0x7fffffff)
         return set_err(PP_ERR_CAPACITY, "RRT* batch too large");
+    if ((r = check_coords(starts, q, 3, "starts")) || (r = check_coords(starts + 1, q, 3, "starts")))
+        return r;
     const size_t rows = (size_t)q * (size_t)cap64, tb = (size_t)q * kStarKMax;
     StarBatch& s = ctx->star;
     s.valid = false;

@@ -21,6 +21,15 @@ int check_ctx(pp_ctx* c, bool need_scene, bool need_rrt) {
     return PP_OK;
 }
 
+int check_coords(const double* v, int64_t n, int64_t stride, const char* what) {
+    if (!v) return PP_OK;
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::fabs(v[i * stride]) <= PP_COORD_MAX))  // (NaN fails the comparison too)
+            return set_err(PP_ERR_INVALID_ARGUMENT,
+                           std::string(what) + ": a coordinate is not finite or exceeds PP_COORD_MAX (2^61)");
+    return PP_OK;
+}
+
 int ensure_events(pp_ctx* c, size_t count) {
     while (c->prof.ev.size() < count) {
         hipEvent_t e;
@@ -108,6 +117,12 @@ int pp_device_count(int* n) {
     return PP_OK;
 }
 
+int pp_coord_check(const double* x, const double* y, int64_t n) {
+    if (n < 0) return set_err(PP_ERR_INVALID_ARGUMENT, "n < 0");
+    int r = check_coords(x, n, 1, "x");
+    return r ? r : check_coords(y, n, 1, "y");
+}
+
 int pp_create(int device, pp_ctx** out) {
     if (!out) return set_err(PP_ERR_INVALID_ARGUMENT, "null output");
     *out = nullptr;
@@ -171,6 +186,9 @@ int pp_dubins_path_planning_batch(pp_ctx* ctx, const pp_dubins_config* confs, in
         if (!(confs[i].turn_radius > 0.0) || !(confs[i].step_size > 0.0))
             return set_err(PP_ERR_INVALID_ARGUMENT, "turn_radius and step_size must be > 0");
     static_assert(sizeof(pp_dubins_config) == 8 * sizeof(double), "DubinsConfig layout");
+    for (int o : {0, 1, 3, 4})  // sx, sy, ex, ey
+        if ((r = check_coords(reinterpret_cast<const double*>(confs) + o, n, 8, "dubins end points")))
+            return r;
     return dubins_batch(ctx, reinterpret_cast<const double*>(confs), 8, launch_dubins_batch, n, cap,
                         px, py, pyaw, n_points, word, cost);
 }
@@ -186,6 +204,8 @@ int pp_dubins_path_planning_from_origin_batch(pp_ctx* ctx, const double* conf5, 
     for (int i = 0; i < n; ++i)
         if (!(conf5[5 * i + 4] > 0.0))
             return set_err(PP_ERR_INVALID_ARGUMENT, "step_size must be > 0");
+    for (int o : {0, 1})  // dx, dy
+        if ((r = check_coords(conf5 + o, n, 5, "dubins end point"))) return r;
     return dubins_batch(ctx, conf5, 5, launch_dubins_origin, n, cap, px, py, pyaw, n_points, word,
                         cost);
 }
@@ -208,6 +228,30 @@ int pp_dubins_words_batch(pp_ctx* ctx, const double* abd, int n, double* tpq, in
     static_assert(sizeof(int) == sizeof(int32_t), "ok words");
     PP_HIP(hipMemcpyAsync(tpq, dtpq.p, 18 * nn * sizeof(double), hipMemcpyDeviceToHost, st));
     PP_HIP(hipMemcpyAsync(ok, dok.p, 6 * nn * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    return PP_OK;
+}
+
+int pp_sincos_small_batch(pp_ctx* ctx, const double* x, int n, double* s, double* c,
+                          double* s_ocml, double* c_ocml) {
+    int r = check_ctx(ctx, false, false);
+    if (r) return r;
+    if (n < 0 || (n > 0 && (!x || !s || !c || !s_ocml || !c_ocml)))
+        return set_err(PP_ERR_INVALID_ARGUMENT, "bad sincos arguments");
+    for (int i = 0; i < n; ++i)
+        if (!(std::fabs(x[i]) < 0x1p30))
+            return set_err(PP_ERR_INVALID_ARGUMENT, "sincos_small takes |x| < 2^30");
+    if (n == 0) return PP_OK;
+    const size_t nn = (size_t)n;
+    DBuf<double> dx, dout;
+    PP_HIP(dx.reserve(nn));
+    PP_HIP(dout.reserve(4 * nn));
+    hipStream_t st = ctx->stream;
+    PP_HIP(hipMemcpyAsync(dx.p, x, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    PP_HIP(launch_sincos_small(st, dx.p, n, dout.p, dout.p + nn, dout.p + 2 * nn, dout.p + 3 * nn));
+    double* out[4] = {s, c, s_ocml, c_ocml};
+    for (int k = 0; k < 4; ++k)
+        PP_HIP(hipMemcpyAsync(out[k], dout.p + k * nn, nn * sizeof(double), hipMemcpyDeviceToHost, st));
     PP_HIP(hipStreamSynchronize(st));
     return PP_OK;
 }

@@ -285,6 +285,9 @@ struct Finish {
     DBuf<SceneDev> scene;   // check_finish_kernel's scene (its step may be a batch's)
     SceneDev scene_host{};  // what `scene` holds (the source of its last upload)
     bool scene_ok = false;
+    // the last cf_run's one line was counted, not stored (cf_line_kernel's error bit 32:
+    // finalize's unverified line past the point capacity)
+    bool counted_only = false;
     DBuf<int> nodes, ok, npts, chain, etab, err, path, items;
     DBuf<int> lpath, spill;  // cf_line_kernel's ancestor paths; tier 1's spill list
     DBuf<int> memo;  // check_finish_kernel's optimize memo (CfBatch::ftab / gtab), per launch
@@ -488,6 +491,10 @@ struct pp_ctx {
 namespace ppamd {
 
 int check_ctx(pp_ctx* c, bool need_scene, bool need_rrt);
+// The coordinates v[0], v[stride], ... (n of them; a null v passes) are finite and at most
+// PP_COORD_MAX in magnitude, else PP_ERR_INVALID_ARGUMENT naming `what`: every entry point that
+// takes positions runs this on the host before it launches anything (pp_coord_check's test).
+int check_coords(const double* v, int64_t n, int64_t stride, const char* what);
 int ensure_events(pp_ctx* c, size_t count);
 // reserve the API literal scratch pool and (once, zeroed on `st`) its slot locks
 int ensure_literal_pool(pp_ctx* c, hipStream_t st);

@@ -151,7 +151,8 @@ int cf_run(pp_ctx* c, const TreeDev& tr, const int* nodes, int k, int want_line,
         c->prof.finish_ms += ms;
         c->prof.finish_launches += 1;
     }
-    return cf_error(err);
+    c->cf.counted_only = (err & 32) != 0;
+    return cf_error(err & ~32);
 }
 
 // pp_batch_plan's check_finish in steer rounds (CfbArgs, pp_kernels.hip): phase A rounds fill
@@ -583,8 +584,9 @@ int pp_rrt_finalize(pp_ctx* ctx, double gx, double gy, double gyaw, int32_t pare
                     double* y, int64_t cap, int64_t* n, uint8_t* verified) {
     int r = check_ctx(ctx, true, true);
     if (r) return r;
-    if (!n || parent < 0 || parent >= ctx->rrt.n || !std::isfinite(gx) || !std::isfinite(gy))
-        return set_err(PP_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (!n || parent < 0 || parent >= ctx->rrt.n || !(std::fabs(gx) <= PP_COORD_MAX) ||
+        !(std::fabs(gy) <= PP_COORD_MAX))
+        return set_err(PP_ERR_INVALID_ARGUMENT, "bad arguments (the goal: finite, within PP_COORD_MAX)");
     CfGoal g{gx, gy, gyaw, ctx->rrt.goal[2]};
     g.mode = kCfFinalize;
     if ((r = cf_launch_one(ctx, parent, 1, &g))) return r;
@@ -596,6 +598,9 @@ int pp_rrt_finalize(pp_ctx* ctx, double gx, double gy, double gyaw, int32_t pare
     *n = np;
     if (!(x && y) || cap == 0) return PP_OK;
     if (cap < np) return set_err(PP_ERR_CAPACITY, "line buffer smaller than the finalized line");
+    // (an unverified line of more than 65536 points is counted on the device, never stored)
+    if (ctx->cf.counted_only)
+        return set_err(PP_ERR_CAPACITY, "finalized line longer than the point capacity");
     return cf_copy_line(ctx, row[1], x, y, n);
 }
 

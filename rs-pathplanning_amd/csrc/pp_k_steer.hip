@@ -87,6 +87,28 @@ __global__ __launch_bounds__(64) void dubins_words_kernel(const double* __restri
     }
 }
 
+// pp_sincos_small_batch: the walk's sincos_small on the walk's own table (read as the walk reads
+// it, behind an opaque pointer) beside the math library's sincos, both compiled with this unit's
+// flags; |x| < 2^30 (the host checked)
+__global__ __launch_bounds__(256) void sincos_small_kernel(const double* __restrict__ x, int n,
+                                                           double* __restrict__ s,
+                                                           double* __restrict__ c,
+                                                           double* __restrict__ s_ocml,
+                                                           double* __restrict__ c_ocml) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const double* tab = kSinCosTab;
+    asm volatile("" : "+s"(tab));
+    const double v = x[i];
+    double s0, c0, s1, c1;
+    sincos_small(v, tab, &s0, &c0);
+    sincos(v, &s1, &c1);
+    s[i] = s0;
+    c[i] = c0;
+    s_ocml[i] = s1;
+    c_ocml[i] = c1;
+}
+
 // Task t of a window: t < W is (sample t → its snapshot NN); t >= W is candidate entry t - W
 // (sample E.j → window sample E.i, with E.i's yaw under ITS snapshot parent: the speculation the
 // resolve validates).
@@ -470,6 +492,13 @@ hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int c
 hipError_t launch_dubins_words(hipStream_t st, const double* abd, int n, double* tpq, int* ok) {
     if (n <= 0) return hipSuccess;
     dubins_words_kernel<<<(n + 63) / 64, 64, 0, st>>>(abd, n, tpq, ok);
+    return hipGetLastError();
+}
+
+hipError_t launch_sincos_small(hipStream_t st, const double* x, int n, double* s, double* c,
+                               double* s_ocml, double* c_ocml) {
+    if (n <= 0) return hipSuccess;
+    sincos_small_kernel<<<(n + 255) / 256, 256, 0, st>>>(x, n, s, c, s_ocml, c_ocml);
     return hipGetLastError();
 }
 

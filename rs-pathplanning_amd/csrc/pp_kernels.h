@@ -392,6 +392,9 @@ hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int c
                                 double* cost_out, int* status_out);
 // the six Dubins words of n (alpha, beta, d) triples
 hipError_t launch_dubins_words(hipStream_t st, const double* abd, int n, double* tpq, int* ok);
+// sincos_small on the library's table and the math library's sincos of n arguments (|x| < 2^30)
+hipError_t launch_sincos_small(hipStream_t st, const double* x, int n, double* s, double* c,
+                               double* s_ocml, double* c_ocml);
 
 hipError_t launch_dubins_batch(hipStream_t st, const double* conf, int n, int cap, double* px,
                                double* py, double* pyaw, int* n_out, int* word_out,

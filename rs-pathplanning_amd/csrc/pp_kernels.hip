@@ -2190,6 +2190,10 @@ static_assert(kCfLineThreads == 64, "cf_line_kernel: one wave per item (its edge
 // indices below the last one whose local x is nonzero (none: 0), or all n_point when the last
 // slot is written and nonzero.  Returns kSteerSome / kSteerNone / kSteerOverflow like the
 // literal restatement.
+// kCount: the kept count alone — nothing is stored (px / py / cap unused), so an edge of up to
+// 2e9 steps is counted where the storing form stops at 1e8 steps and at its buffer: finalize's
+// answer for a goal too far for the line buffer (the same chain of values, the same trim).
+template <bool kCount = false>
 __device__ int line_edge_wave(double sx, double sy, double syaw, const double* __restrict__ word,
                               double turn_radius, double step_size, double* px, double* py,
                               int cap, int lane, int* n_out) {
@@ -2208,9 +2212,9 @@ __device__ int line_edge_wave(double sx, double sy, double syaw, const double* _
     total += s.p;
     total += s.q;
     const double nq = trunc(total / step_size);
-    if (!(nq >= 0.0) || nq > 1.0e8) return kSteerOverflow;
+    if (!(nq >= 0.0) || nq > (kCount ? 2.0e9 : 1.0e8)) return kSteerOverflow;
     const int n_point = (int)nq + 3 + 4;
-    if (n_point > cap) return kSteerOverflow;
+    if (!kCount && n_point > cap) return kSteerOverflow;
     // every sin / cos the edge needs in one lane-parallel round (the same calls on the same
     // arguments as interp_local and the world transform make, so the same values): lanes 0..2 the
     // segment origins' yaw trig (S: cos / sin of the yaw; L, R: of minus the yaw), 3..5 sin / cos
@@ -2231,7 +2235,7 @@ __device__ int line_edge_wave(double sx, double sy, double syaw, const double* _
     }
     const double sv = sin(arg), cv = cos(arg);
     const double cs = readlane_f64(cv, 6), sn = readlane_f64(sv, 6);
-    if (lane == 0) {  // the origin, index 0
+    if (!kCount && lane == 0) {  // the origin, index 0
         px[0] = cs * 0.0 + sn * 0.0 + sx;
         py[0] = -sn * 0.0 + cs * 0.0 + sy;
     }
@@ -2292,8 +2296,10 @@ __device__ int line_edge_wave(double sx, double sy, double syaw, const double* _
                     lx = o.x + (cmo * ldx + smo * ldy);
                     ly = o.y + (-smo * ldx + cmo * ldy);
                 }
-                px[base + lane] = cs * lx + sn * ly + sx;
-                py[base + lane] = -sn * lx + cs * ly + sy;
+                if (!kCount) {
+                    px[base + lane] = cs * lx + sn * ly + sx;
+                    py[base + lane] = -sn * lx + cs * ly + sy;
+                }
                 const uint64_t nz = __ballot(lx != 0.0);
                 if (nz) lastnz = base + 63 - (int)__builtin_clzll(nz);
                 lastx = lx;
@@ -2326,7 +2332,7 @@ __device__ int line_edge_wave(double sx, double sy, double syaw, const double* _
         }
         r.yaw = 0.0;  // (the next segment's trig comes from the round)
         if (i == 2) {
-            if (lane == 0) {
+            if (!kCount && lane == 0) {
                 px[ind] = cs * r.x + sn * r.y + sx;
                 py[ind] = -sn * r.x + cs * r.y + sy;
             }
@@ -2359,12 +2365,15 @@ __device__ inline void cf_spill(const CfLineBufs& lb, const int* __restrict__ o,
     }
 }
 
+// kCountLong (finalize's one-node launch only: the instantiation the plans run has none of it):
+// an unverified line too long for the buffer at the full capacity is counted instead of stored.
+template <bool kCountLong>
 __global__ __launch_bounds__(kCfLineThreads) void cf_line_kernel(
     SceneDev sc, TreeDev tr_in, const int* __restrict__ nodes, double gx_in, double gy_in,
     double gyaw_in, double gyaw_opt_in, int* __restrict__ ok_out, double* __restrict__ len_out,
     int* __restrict__ npts_out, CfLineBufs lb, int* __restrict__ err, CfBatch cb,
     const int* __restrict__ items) {
-    __shared__ int s_off, s_bad;
+    __shared__ int s_off, s_bad, s_count;
     __shared__ int s_pos[kCfLevels];
     const int tid = threadIdx.x;
     // this workgroup's buffers: points (x, y, hypots / words), edge table, ancestor path
@@ -2419,7 +2428,10 @@ __global__ __launch_bounds__(kCfLineThreads) void cf_line_kernel(
             const int node = path[ps - (j - s - 1)];
             return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
         };
-        if (tid == 0) s_bad = 0;
+        if (tid == 0) {
+            s_bad = 0;
+            if (kCountLong) s_count = 0;
+        }
         // every edge's word and point count, a lane per edge; the words wait in the hypot buffer
         // (4 doubles an edge, 4 kCfMaxEdges <= pts_cap) for the generation below
         for (int e = tid; e < E; e += kCfLineThreads) {
@@ -2455,7 +2467,25 @@ __global__ __launch_bounds__(kCfLineThreads) void cf_line_kernel(
             __syncthreads();
             continue;
         }
-        if (total < 0) {
+        if (kCountLong && total == -1 && !vok && !lb.spill) {
+            // finalize's unverified line, too long for the buffer at the full capacity (a goal
+            // far outside the scene): its points are counted, not stored — no length, error bit
+            // 32 tells the host that the line itself is not there
+            const int lane = tid & 63;
+            for (int e = tid >> 6; e < E; e += kCfLineThreads / 64) {
+                const CfPose a = pose(e);
+                int n = 0;
+                const int r = line_edge_wave<true>(a.x, a.y, a.yaw, pyw + 4 * (size_t)e,
+                                                   sc.turn_radius, sc.step_size, nullptr, nullptr,
+                                                   0, lane, &n);
+                if (lane == 0) {
+                    et[2 * e + 1] = r == kSteerSome ? n : 0;
+                    if (r == kSteerNone) atomicOr(&s_bad, 2);
+                    else if (r != kSteerSome) atomicOr(&s_bad, 4);
+                }
+            }
+            if (tid == 0) s_count = 1;
+        } else if (total < 0) {
             if (tid == 0) s_bad = total == -2 ? 2 : 8;
         } else {
             const int lane = tid & 63;
@@ -2481,7 +2511,8 @@ __global__ __launch_bounds__(kCfLineThreads) void cf_line_kernel(
         // (f + 1 -> f) for f = np - 2 down to 0.  Every segment's hypot in parallel (into the
         // yaw buffer, by forward index), then one lane adds them in the reversed order — the
         // same operands, the same order of the sum
-        const int bad0 = s_bad;
+        const int counted = kCountLong ? s_count : 0;
+        const int bad0 = s_bad | counted;  // (a counted line has no points to measure)
         LT(3)
         int npts_all = 0;
         if (bad0 == 0 && E <= 64) {
@@ -2537,8 +2568,13 @@ __global__ __launch_bounds__(kCfLineThreads) void cf_line_kernel(
             // chunk's load in flight), added in lane order by readlane — the serial order
             double len = 0.0;
             int npts = 0;
-            const int bad = s_bad;
-            if (bad == 0) {
+            int bad = s_bad;
+            if (bad == 0 && counted) {
+                long long sum = 0;
+                for (int e = 0; e < E; ++e) sum += et[2 * e + 1];
+                if (sum > 0x7fffffffll) bad = 8;
+                npts = (int)sum;
+            } else if (bad == 0) {
                 npts = npts_all;
                 int hi = npts - 2;
                 double v = hi - tid >= 0 ? pyw[hi - tid] : 0.0;
@@ -2558,6 +2594,7 @@ __global__ __launch_bounds__(kCfLineThreads) void cf_line_kernel(
                 len_out[b] = bad == 0 ? len : 0.0;
                 npts_out[b] = bad == 0 ? npts : 0;
                 if (bad) atomicOr(err, bad);
+                else if (counted) atomicOr(err, 32);
             }
         }
         __syncthreads();  // the buffers and s_off serve the next item
@@ -2588,11 +2625,14 @@ hipError_t launch_check_finish(hipStream_t st, const SceneDev& sc, const SceneDe
                                                         chain, lit_scratch, lit_locks, err, tally,
                                                         cb, gpath, items, blist);
     if (want_line && mode != kCfOptimize && lines.grid1 > 0) {
-        cf_line_kernel<<<lines.grid1, kCfLineThreads, 0, st>>>(sc, tr, nodes, gx, gy, gyaw,
-                                                               gyaw_opt, ok, len, npts, lines.t1,
-                                                               err, cb, items);
+        if (mode == kCfFinalize && !lines.t1.spill)  // (one node: a far goal's line is counted)
+            cf_line_kernel<true><<<lines.grid1, kCfLineThreads, 0, st>>>(
+                sc, tr, nodes, gx, gy, gyaw, gyaw_opt, ok, len, npts, lines.t1, err, cb, items);
+        else
+            cf_line_kernel<false><<<lines.grid1, kCfLineThreads, 0, st>>>(
+                sc, tr, nodes, gx, gy, gyaw, gyaw_opt, ok, len, npts, lines.t1, err, cb, items);
         if (lines.t1.spill)  // the lines past tier 1's capacities, at the full ones
-            cf_line_kernel<<<lines.grid2, kCfLineThreads, 0, st>>>(sc, tr, nodes, gx, gy, gyaw,
+            cf_line_kernel<false><<<lines.grid2, kCfLineThreads, 0, st>>>(sc, tr, nodes, gx, gy, gyaw,
                                                                    gyaw_opt, ok, len, npts,
                                                                    lines.t2, err, cb,
                                                                    lines.t1.spill);

@@ -122,6 +122,8 @@ int pp_rrt_new(pp_ctx* ctx, double sx, double sy, double syaw, double gx, double
     if (r) return r;
     if (!(step_size > 0.0) || max_iter < 0)
         return set_err(PP_ERR_INVALID_ARGUMENT, "step_size must be > 0 and max_iter >= 0");
+    const double ends[4] = {sx, sy, gx, gy};
+    if ((r = check_coords(ends, 4, 1, "start and goal"))) return r;
     ctx->rrt.valid = false;
     ctx->rrt.stale = false;
     PP_HIP(hipStreamSynchronize(ctx->stream));
@@ -210,7 +212,7 @@ int rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted, const Samp
         s.it += n_iter;
         s.it_spec = s.it;
         s.iterations += n_iter;
-        s.node_evals += n_iter;  // the NN of every iteration scans the root
+        s.node_evals += n_iter * ctx->rrt.n;  // the NN of every iteration scans the fixed tree
         PP_HIP(hipMemcpy(ctx->rrt.d_state.p, &s, sizeof(DevState), hipMemcpyHostToDevice));
         ctx->rrt.it = s.it;
         if (n_accepted) *n_accepted = 0;
@@ -282,6 +284,35 @@ int rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted, const Samp
 // pp_rrt_extend_samples' device buffers: samples and records of kHostChunk iterations at a time
 constexpr int64_t kHostChunk = (int64_t)1 << 20;
 
+// RRT::get_nearest_node of k points on the tree as it stands, Kcap points a launch.  eps: the f32
+// screen's tolerance for this call — the planner's own, widened by the caller's points where they
+// are larger than anything the scene bounds (their f32 copies round by up to |q| 2^-24).
+int nearest_batch(pp_ctx* ctx, const double* qx, const double* qy, int k, int32_t* idx, double* d2,
+                  double eps) {
+    hipStream_t st = ctx->stream;
+    WindowArgs a = ctx->rrt.window_args(ctx->scene_dev(), ctx->prof.points(), ctx->rrt.d_api_state.p);
+    a.eps_coord = eps;
+    for (int b = 0; b < k; b += ctx->rrt.Kcap) {
+        const int nb = std::min(ctx->rrt.Kcap, k - b);
+        DevState* hs = &ctx->rrt.h_state.p[1];
+        *hs = DevState{};
+        hs->W = nb;
+        hs->Wp[0] = nb;
+        hs->n = (int)ctx->rrt.n;
+        hs->nsp[0] = (int)ctx->rrt.n;
+        hs->n_scan = (int)ctx->rrt.n;
+        hs->void_seq = -1;
+        PP_HIP(hipMemcpyAsync(ctx->rrt.d_api_state.p, hs, sizeof(DevState), hipMemcpyHostToDevice, st));
+        PP_HIP(hipMemcpyAsync(ctx->rrt.wsx.p, qx + b, nb * sizeof(double), hipMemcpyHostToDevice, st));
+        PP_HIP(hipMemcpyAsync(ctx->rrt.wsy.p, qy + b, nb * sizeof(double), hipMemcpyHostToDevice, st));
+        PP_HIP(launch_nearest(st, a));
+        PP_HIP(hipMemcpyAsync(idx + b, ctx->rrt.nn_idx.p, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (d2) PP_HIP(hipMemcpyAsync(d2 + b, ctx->rrt.nn_d2.p, nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        PP_HIP(hipStreamSynchronize(st));
+    }
+    return PP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -305,21 +336,24 @@ int pp_rrt_extend_samples(pp_ctx* ctx, const double* sx, const double* sy, int64
             return set_err(PP_ERR_INVALID_ARGUMENT, "a sample is not finite");
         mx = std::max({mx, std::fabs(sx[i]), std::fabs(sy[i])});
     }
+    if (mx > PP_COORD_MAX) return set_err(PP_ERR_INVALID_ARGUMENT, "a sample exceeds PP_COORD_MAX");
     // the f32 screen's tolerance covers the coordinates it rounds: nodes and these samples
     const double eps = std::max(ctx->rrt.eps_coord, mx * std::ldexp(1.0, -23));
     int64_t acc_all = 0;
     if (ctx->rrt.root_blocked) {  // nothing is ever inserted: the tree is fixed, every verdict false
-        const int64_t n_before = ctx->rrt.n;
-        for (int64_t b = 0; b < k && (nearest || yaw); b += ctx->rrt.Kcap) {
-            const int nb = (int)std::min<int64_t>(ctx->rrt.Kcap, k - b);
-            std::vector<int32_t> idx((size_t)nb);
-            if ((r = pp_rrt_get_nearest_node_batch(ctx, sx + b, sy + b, nb, idx.data(), nullptr)))
-                return r;
-            std::vector<double> tx((size_t)n_before), ty((size_t)n_before);
-            if (yaw) {
-                PP_HIP(hipMemcpy(tx.data(), ctx->rrt.X.p, tx.size() * sizeof(double), hipMemcpyDeviceToHost));
-                PP_HIP(hipMemcpy(ty.data(), ctx->rrt.Y.p, ty.size() * sizeof(double), hipMemcpyDeviceToHost));
-            }
+        const size_t n_before = (size_t)ctx->rrt.n;
+        std::vector<double> tx, ty;  // the fixed tree, read once
+        if (yaw && k > 0) {
+            tx.resize(n_before);
+            ty.resize(n_before);
+            PP_HIP(hipMemcpy(tx.data(), ctx->rrt.X.p, n_before * sizeof(double), hipMemcpyDeviceToHost));
+            PP_HIP(hipMemcpy(ty.data(), ctx->rrt.Y.p, n_before * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        std::vector<int32_t> idx;
+        for (int64_t b = 0; b < k && (nearest || yaw); b += kHostChunk) {
+            const int nb = (int)std::min(kHostChunk, k - b);
+            idx.resize((size_t)nb);
+            if ((r = nearest_batch(ctx, sx + b, sy + b, nb, idx.data(), nullptr, eps))) return r;
             for (int i = 0; i < nb; ++i) {
                 if (nearest) nearest[b + i] = idx[(size_t)i];
                 if (yaw) yaw[b + i] = std::atan2(ty[(size_t)idx[i]] - sy[b + i], tx[(size_t)idx[i]] - sx[b + i]);
@@ -376,6 +410,7 @@ int pp_rrt_tree_import(pp_ctx* ctx, const double* x, const double* y, const doub
             return set_err(PP_ERR_INVALID_ARGUMENT, "a node coordinate is not finite");
         mx = std::max({mx, std::fabs(x[i]), std::fabs(y[i])});
     }
+    if (mx > PP_COORD_MAX) return set_err(PP_ERR_INVALID_ARGUMENT, "a node exceeds PP_COORD_MAX");
     PP_HIP(hipStreamSynchronize(ctx->stream));
     if ((r = ensure_tree(ctx, n + 1024))) return r;
     if ((r = upload_tree(ctx, x, y, yaw, parent, (size_t)n))) return r;
@@ -508,27 +543,12 @@ int pp_rrt_get_nearest_node_batch(pp_ctx* ctx, const double* qx, const double* q
     int r = check_ctx(ctx, true, true);
     if (r) return r;
     if (k < 0 || (k > 0 && (!qx || !qy || !idx))) return set_err(PP_ERR_INVALID_ARGUMENT, "bad arguments");
-    hipStream_t st = ctx->stream;
-    WindowArgs a = ctx->rrt.window_args(ctx->scene_dev(), ctx->prof.points(), ctx->rrt.d_api_state.p);
-    for (int b = 0; b < k; b += ctx->rrt.Kcap) {
-        const int nb = std::min(ctx->rrt.Kcap, k - b);
-        DevState* hs = &ctx->rrt.h_state.p[1];
-        *hs = DevState{};
-        hs->W = nb;
-        hs->Wp[0] = nb;
-        hs->n = (int)ctx->rrt.n;
-        hs->nsp[0] = (int)ctx->rrt.n;
-        hs->n_scan = (int)ctx->rrt.n;
-        hs->void_seq = -1;
-        PP_HIP(hipMemcpyAsync(ctx->rrt.d_api_state.p, hs, sizeof(DevState), hipMemcpyHostToDevice, st));
-        PP_HIP(hipMemcpyAsync(ctx->rrt.wsx.p, qx + b, nb * sizeof(double), hipMemcpyHostToDevice, st));
-        PP_HIP(hipMemcpyAsync(ctx->rrt.wsy.p, qy + b, nb * sizeof(double), hipMemcpyHostToDevice, st));
-        PP_HIP(launch_nearest(st, a));
-        PP_HIP(hipMemcpyAsync(idx + b, ctx->rrt.nn_idx.p, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (d2) PP_HIP(hipMemcpyAsync(d2 + b, ctx->rrt.nn_d2.p, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-        PP_HIP(hipStreamSynchronize(st));
-    }
-    return PP_OK;
+    if ((r = check_coords(qx, k, 1, "query points")) || (r = check_coords(qy, k, 1, "query points")))
+        return r;
+    double mx = 0.0;
+    for (int i = 0; i < k; ++i) mx = std::max({mx, std::fabs(qx[i]), std::fabs(qy[i])});
+    return nearest_batch(ctx, qx, qy, k, idx, d2,
+                         std::max(ctx->rrt.eps_coord, mx * std::ldexp(1.0, -23)));
 }
 
 int pp_rrt_verify_node_batch(pp_ctx* ctx, const double* x, const double* y,
@@ -539,6 +559,8 @@ int pp_rrt_verify_node_batch(pp_ctx* ctx, const double* x, const double* y,
     for (int i = 0; i < k; ++i)
         if (parent[i] < 0 || parent[i] >= ctx->rrt.n)
             return set_err(PP_ERR_INVALID_ARGUMENT, "parent index outside the tree");
+    if ((r = check_coords(x, k, 1, "candidates")) || (r = check_coords(y, k, 1, "candidates")))
+        return r;
     hipStream_t st = ctx->stream;
     const SceneDev sc = ctx->scene_dev();
     const TreeDev tr = ctx->rrt.tree_dev();

@@ -61,8 +61,9 @@ int disc_scene(double x0, double y0, double x1, double y1, double robot_width, c
     s.items = Items{};
     double mx = std::max({std::fabs(s.minx), std::fabs(s.maxx), std::fabs(s.miny), std::fabs(s.maxy)});
     for (int k = 0; k < m; ++k) {
-        if (!std::isfinite(cx[k]) || !std::isfinite(cy[k]) || !std::isfinite(r[k]))
-            return fail(err, PP_ERR_INVALID_ARGUMENT, "non-finite obstacle disc");
+        if (!(std::fabs(cx[k]) <= PP_COORD_MAX) || !(std::fabs(cy[k]) <= PP_COORD_MAX) ||
+            !(std::fabs(r[k]) <= PP_COORD_MAX))
+            return fail(err, PP_ERR_INVALID_ARGUMENT, "obstacle disc not finite or beyond PP_COORD_MAX");
         const double reff = r[k] + half;
         const double rc = reff * (1.0 + 1e-9) + 1e-9;
         s.r2[k] = reff * reff;
@@ -85,8 +86,8 @@ int polygon_scene(const double* bounds_xy, int nb, const double* obs_xy, const i
     ring(bounds_xy, nb, s.bvx, s.bvy);
     if (s.bvx.size() < 3) return fail(err, PP_ERR_INVALID_ARGUMENT, "bounds ring has < 3 vertices");
     for (size_t i = 0; i < s.bvx.size(); ++i)
-        if (!std::isfinite(s.bvx[i]) || !std::isfinite(s.bvy[i]))
-            return fail(err, PP_ERR_INVALID_ARGUMENT, "non-finite bounds vertex");
+        if (!(std::fabs(s.bvx[i]) <= PP_COORD_MAX) || !(std::fabs(s.bvy[i]) <= PP_COORD_MAX))
+            return fail(err, PP_ERR_INVALID_ARGUMENT, "bounds vertex not finite or beyond PP_COORD_MAX");
     // Space::new, rrt.rs:82-106: rand_point samples the bbox of the shrunken bounds — here the
     // bounds' bbox shrunk by width/2, which contains the eroded polygon (Q10p)
     const double half = robot_width / 2.0;
@@ -113,8 +114,8 @@ int polygon_scene(const double* bounds_xy, int nb, const double* obs_xy, const i
         ring(obs_xy + 2 * (size_t)a, b - a, vx, vy);
         const int n = (int)vx.size();
         for (int i = 0; i < n; ++i) {
-            if (!std::isfinite(vx[i]) || !std::isfinite(vy[i]))
-                return fail(err, PP_ERR_INVALID_ARGUMENT, "non-finite obstacle vertex");
+            if (!(std::fabs(vx[i]) <= PP_COORD_MAX) || !(std::fabs(vy[i]) <= PP_COORD_MAX))
+                return fail(err, PP_ERR_INVALID_ARGUMENT, "obstacle vertex not finite or beyond PP_COORD_MAX");
             const int j = i + 1 == n ? 0 : i + 1;
             s.ex0.push_back(vx[i]);
             s.ey0.push_back(vy[i]);

@@ -111,7 +111,9 @@ int pp_space_new(pp_ctx* ctx, double x0, double y0, double x1, double y1, double
     if (rc) return rc;
     if (!(robot_width >= 0.0) || !(max_steer > 0.0))
         return set_err(PP_ERR_INVALID_ARGUMENT, "robot width must be >= 0 and max_steer > 0");
-    scene::DiscScene ds;
+    const double box[4] = {x0, y0, x1, y1};
+    if ((rc = check_coords(box, 4, 1, "bounds"))) return rc;
+    scene::DiscScene ds;  // (disc_scene checks the discs against PP_COORD_MAX)
     std::string err;
     if ((rc = scene::disc_scene(x0, y0, x1, y1, robot_width, cx, cy, r, m, &ds, &err)))
         return set_err(rc, err);
@@ -149,7 +151,7 @@ int pp_space_new_polygons(pp_ctx* ctx, const double* bounds_xy, int nb, const do
         return set_err(PP_ERR_INVALID_ARGUMENT, "bad polygon arrays (bounds need >= 3 vertices)");
     if (!(robot_width >= 0.0) || !(max_steer > 0.0))
         return set_err(PP_ERR_INVALID_ARGUMENT, "robot width must be >= 0 and max_steer > 0");
-    scene::PolygonScene ps;
+    scene::PolygonScene ps;  // (polygon_scene checks the vertices against PP_COORD_MAX)
     std::string err;
     if ((rc = scene::polygon_scene(bounds_xy, nb, obs_xy, obs_off, n_obs, robot_width, &ps, &err)))
         return set_err(rc, err);
@@ -182,6 +184,8 @@ int pp_space_set_grid(pp_ctx* ctx, const uint32_t* bits, int w, int h, double x0
     if (rc) return rc;
     if (!bits || w <= 0 || h <= 0 || w > (1 << 16) || h > (1 << 16) || !(cell > 0.0))
         return set_err(PP_ERR_INVALID_ARGUMENT, "bad occupancy grid");
+    const double corners[4] = {x0, y0, x0 + w * cell, y0 + h * cell};
+    if ((rc = check_coords(corners, 4, 1, "grid corners"))) return rc;
     const int words = (w + 31) / 32;
     const size_t n = (size_t)words * h;
     Scene& s = ctx->scene;
@@ -217,6 +221,8 @@ int pp_space_verify_batch(pp_ctx* ctx, const double* x, const double* y, const i
         if (off[i + 1] < off[i]) return set_err(PP_ERR_INVALID_ARGUMENT, "off must be non-decreasing");
     const int64_t np = off[k];
     if (np > 0 && (!x || !y)) return set_err(PP_ERR_INVALID_ARGUMENT, "null points");
+    if ((r = check_coords(x, np, 1, "line points")) || (r = check_coords(y, np, 1, "line points")))
+        return r;
     hipStream_t st = ctx->stream;
     DBuf<double> dx, dy;
     DBuf<int64_t> doff;

@@ -15,7 +15,10 @@ int star_ready(pp_ctx* ctx) {
     return PP_OK;
 }
 
-bool finite3(const double* g) { return std::isfinite(g[0]) && std::isfinite(g[1]) && std::isfinite(g[2]); }
+// a goal pose: finite, its position within PP_COORD_MAX
+bool finite3(const double* g) {
+    return std::fabs(g[0]) <= PP_COORD_MAX && std::fabs(g[1]) <= PP_COORD_MAX && std::isfinite(g[2]);
+}
 
 // The goal rounds of the queries [q0, q1) on the context's stream: goals = 3 doubles per served
 // query.  One read of the tree sizes gives the round count, the rounds are enqueued back to back,

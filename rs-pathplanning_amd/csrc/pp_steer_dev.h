@@ -559,6 +559,16 @@ __device__ __forceinline__ bool point_blocked(const SceneDev& sc, double x, doub
 //               (dubins.rs:239-255) replayed uniformly, each lane capturing one grid point so
 //               every point carries exactly the reference's accumulated value; interpolation
 //               and the collision test then run lane-parallel, 63 points per chunk.
+// An edge too long to walk (more than 1e8 steps: the reference would allocate that many points)
+// is an error, unless its verdict is known without the walk: the line starts at the child
+// (point 0 of the Dubins polyline, and the None line's first point), and Space::verify rejects a
+// line with a point outside the bounds' box in every scene mode (chunk_rejects' first test).  A
+// caller's sample or candidate far outside the scene is such a child: rejected, its nearest node
+// and yaw still reported.
+__device__ __forceinline__ bool child_out_of_bounds(const SceneDev& sc, double x, double y) {
+    return !(x >= sc.minx && x <= sc.maxx && y >= sc.miny && y <= sc.maxy);
+}
+
 struct SteerPrep {
     double x, y, px, py;      // child (point 0 of the edge) and parent (the junction)
     double c, cw, sw;         // curvature, cos/sin(-yaw) of the world transform
@@ -605,7 +615,7 @@ __device__ __forceinline__ SteerPrep steer_prep(const SceneDev& sc, double x, do
     total += s.q;
     const double nq = trunc(total / step);
     if (!(nq >= 0.0) || nq > 1.0e8) {
-        r.state = kError;
+        r.state = child_out_of_bounds(sc, x, y) ? kReject : kError;
         return r;
     }
     r.n_point = (long long)nq + 3 + 4;
@@ -970,7 +980,8 @@ __device__ __forceinline__ void prep_task(const SceneDev& sc, int r, int g0, int
     tot += L1;
     tot += L2;
     const double nq = trunc(tot / step);
-    if (state == kPrepWalk && (!(nq >= 0.0) || nq > 1.0e8)) state = kError;
+    if (state == kPrepWalk && (!(nq >= 0.0) || nq > 1.0e8))
+        state = child_out_of_bounds(sc, x, y) ? kReject : kError;
     // segment origin headings (interpolate's yaw, dubins.rs:191-196)
     const double oy0 = 0.0;
     const double oy1 = m0 == kModeL ? oy0 + L0 : (m0 == kModeR ? oy0 - L0 : oy0);

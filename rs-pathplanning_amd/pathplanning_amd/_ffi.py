@@ -51,7 +51,9 @@ EXPORTED = [
     "pp_star_repair",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
+    "pp_coord_check", "pp_sincos_small_batch",
 ]
+PP_COORD_MAX = 2.0 ** 61
 
 
 class PPError(RuntimeError):
@@ -189,6 +191,8 @@ def lib():
             "pp_rrt_get_stats": ([vp, C.POINTER(StatsC), C.c_uint64], C.c_int),
             "pp_rrt_reset_stats": ([vp], C.c_int),
             "pp_set_profiling": ([vp, C.c_int], C.c_int),
+            "pp_coord_check": ([dp, dp, C.c_int64], C.c_int),
+            "pp_sincos_small_batch": ([vp, dp, C.c_int, dp, dp, dp, dp], C.c_int),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)

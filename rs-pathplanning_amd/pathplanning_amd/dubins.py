@@ -149,6 +149,20 @@ def words_batch(abd, ctx: _ffi.Context | None = None):
     return tpq, ok
 
 
+def sincos_small_batch(x, ctx: _ffi.Context | None = None):
+    """``(s, c, s_ocml, c_ocml)`` of every ``x`` (|x| < 2^30): the steer walk's own sine and
+    cosine on the library's constants, and the HIP math library's from the same build
+    (``pp_sincos_small_batch``; for tests — the two pairs must be bit-equal)."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    n = len(x)
+    ctx = ctx or _ffi.default_context()
+    out = [np.zeros(n) for _ in range(4)]
+    dp = C.POINTER(C.c_double)
+    _ffi.check(_ffi.lib().pp_sincos_small_batch(ctx.handle, x.ctypes.data_as(dp), n,
+                                                *(o.ctypes.data_as(dp) for o in out)))
+    return tuple(out)
+
+
 def _word(w: int, alpha: float, beta: float, d: float):
     tpq, ok = words_batch([(alpha, beta, d)])
     if not ok[0, w]:

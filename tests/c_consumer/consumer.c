@@ -38,6 +38,11 @@ int main(void) {
     printf("], \"mod2pi\": %.17g, \"pi_2_pi\": %.17g, ", pp_mod2pi(-7.25), pp_pi_2_pi(4.0));
     printf("\"rng\": \"%llu\", \"gen_range\": %.17g, ", (unsigned long long)pp_rng_u64(42, 7),
            pp_gen_range(42, 7, -3.0, 5.0));
+    /* the position ceiling: a C compiler reads PP_COORD_MAX as 2^61, and the host-only check
+     * accepts it and refuses twice it */
+    const double at[2] = {PP_COORD_MAX, -PP_COORD_MAX}, above[2] = {0.0, 2.0 * PP_COORD_MAX};
+    printf("\"coord_max\": %.17g, \"rc_at\": %d, \"rc_above\": %d, \"err_arg\": %d, ", PP_COORD_MAX,
+           pp_coord_check(at, at, 2), pp_coord_check(at, above, 2), PP_ERR_INVALID_ARGUMENT);
     printf("\"rc_dev\": %d, \"ndev\": %d, \"ok\": %d, \"err\": %d}\n", rc_dev, ndev, PP_OK,
            PP_ERR_CAPACITY);
     return 0;

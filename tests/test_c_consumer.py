@@ -57,5 +57,7 @@ def test_host_entry_points_through_c(pkg, consumer):
     assert consumer["pi_2_pi"] == dubins_py.pi_2_pi(4.0)
     assert int(consumer["rng"]) == dubins_py.rng_u64(42, 7)
     assert consumer["gen_range"] == dubins_py.gen_range(42, 7, -3.0, 5.0)
+    assert consumer["coord_max"] == 2.0 ** 61 == pkg._ffi.PP_COORD_MAX
+    assert consumer["rc_at"] == consumer["ok"] and consumer["rc_above"] == consumer["err_arg"]
     # pp_device_count never fails on a CPU-only host (header contract)
     assert consumer["rc_dev"] == consumer["ok"] and consumer["ndev"] >= 0
