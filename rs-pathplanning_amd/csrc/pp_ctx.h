@@ -93,6 +93,9 @@ struct Scene {
     DBuf<uint32_t> d_ibits;
     int ibn = 0;
     double ibx0 = 0.0, iby0 = 0.0, ibinv = 1.0;
+    // the share of the pre-test's cells that are set (inside bitmap / occupancy grid): what the
+    // extend loop expects of a window's draws before it has counters of its own (0: no pre-test)
+    double blocked_share = 0.0;
     int ne = 0, nbv = 0;
     double h2 = 0.0;
     float cull_slack = 1.0e-3f;
@@ -189,6 +192,7 @@ struct Planner {
     int64_t it = 0;   // mirror of DevState.it (exact after every synchronisation)
     int64_t seq = 0;  // windows enqueued so far (their sequence numbers)
     int64_t n = 0;    // mirror of DevState.n
+    double blocked_share = -1.0;  // draws in an obstacle per iteration, last batch (< 0: none yet)
     int64_t cap = 0;  // tree capacity
     double eps_coord = 0.0;
     bool root_blocked = false;  // polygon mode: the root fails verify (nothing is ever inserted)
@@ -215,7 +219,7 @@ struct Planner {
     DBuf<CandEntry> cand;
     DBuf<PrepRec> rec;   // per-task steer records
     DBuf<int> r_order, r_rep, pend, fin_par;
-    DBuf<unsigned char> blk;   // [2 Kcap] window samples in an obstacle (point_blocked)
+    DBuf<int> iter_off;        // [2 Kcap] window sample -> its iteration's offset in the window
     DBuf<SceneDev> d_scene;    // the scene in device memory (samples_role, the literal paths)
     DBuf<double> r_repyaw;
     DBuf<double> lit_scratch;  // resolve: one literal buffer per wave
@@ -275,7 +279,8 @@ struct Planner {
         a.lit_scratch = lit_scratch.p;
         a.wg_points = wg_points;
         a.scp = d_scene.p;
-        a.blk = d_scene.p ? blk.p : nullptr;
+        a.iter_off = iter_off.p;
+        a.pretest = d_scene.p ? 1 : 0;
         return a;
     }
 };

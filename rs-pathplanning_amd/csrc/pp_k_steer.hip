@@ -140,8 +140,7 @@ __global__ __launch_bounds__(kPrepThreads) void steer_prep_kernel(
     const DevState* __restrict__ st, SceneDev sc, const double* __restrict__ wsx,
     const double* __restrict__ wsy, const double* __restrict__ snap_pose,
     CandEntry* __restrict__ cand, PrepRec* __restrict__ rec, double* __restrict__ snap_yaw, const SteerTask* __restrict__ tasks,
-    double* __restrict__ cost_out = nullptr, const StarTaskExt* __restrict__ ext = nullptr,
-    const unsigned char* __restrict__ blk_in = nullptr) {
+    double* __restrict__ cost_out = nullptr, const StarTaskExt* __restrict__ ext = nullptr) {
     // tasks != nullptr: explicit (child, parent pose) tasks [0, W) (multi-query batch); a task
     // with pnode < 0 is idle; own_yaw: the child keeps its heading cyaw (RRT* rewire edges)
     const int W = st->W;
@@ -158,8 +157,7 @@ __global__ __launch_bounds__(kPrepThreads) void steer_prep_kernel(
         // t: the slot (the yaw's); list mode reads the compacted task and writes the record at ti
         const int t = (al && valid) ? al[ti] : ti;
         const int ri = al ? ti : t;
-        // (window mode: a sample in an obstacle needs no steer — a kReject record)
-        bool act = valid && !(blk_in && t < W && blk_in[t]);
+        bool act = valid;
         int j = 0, own = 0, cull = 0;
         double x = 0.0, y = 0.0, px = 1.0, py = 0.0, pyaw = 0.0, cyaw = 0.0;
         double cbase = 0.0, climit = 0.0;
@@ -410,10 +408,9 @@ void launch_walk(WalkProfile p, hipStream_t s, int blocks, DevState* st, const S
 
 void launch_prep_window(hipStream_t s, int blocks, const DevState* st, const SceneDev& sc,
                         const double* wsx, const double* wsy, const double* snap_pose,
-                        CandEntry* cand, PrepRec* rec, double* snap_yaw,
-                        const unsigned char* blk) {
+                        CandEntry* cand, PrepRec* rec, double* snap_yaw) {
     steer_prep_kernel<<<blocks, kPrepThreads, 0, s>>>(st, sc, wsx, wsy, snap_pose, cand, rec,
-                                                      snap_yaw, nullptr, nullptr, nullptr, blk);
+                                                      snap_yaw, nullptr, nullptr, nullptr);
 }
 
 void launch_prep_tasks(hipStream_t s, int blocks, const DevState* st, const SceneDev& sc,

@@ -47,7 +47,8 @@ struct WindowArgs {
     double* lit_scratch = nullptr;
     long long* wg_points = nullptr;  // profiling: walked points per walk workgroup (or null)
     const SceneDev* scp = nullptr;  // the scene in device memory (samples_role's point_blocked)
-    unsigned char* blk = nullptr;   // [2 * Kcap] sample in an obstacle (null: no pre-test)
+    int* iter_off = nullptr;        // [2 * Kcap] sample -> its iteration's offset in the window
+    int pretest = 0;                // draws in an obstacle are settled where they are drawn
     // caller-drawn samples (pp_rrt_extend_samples): iteration it's sample is (hsx, hsy)[it -
     // hrec.base] instead of the seeded stream (null: the stream); hrec: the per-iteration record
     const double* hsx = nullptr;

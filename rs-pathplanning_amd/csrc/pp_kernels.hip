@@ -1,6 +1,7 @@
 // pp_kernels.hip — hand-written CDNA4 (gfx950) kernels of the RRT extend hot path.
 //
-// Window pipeline (one speculative window of K iterations, device-resident state):
+// Window pipeline (one speculative window of up to K samples — the draws of up to 2 K iterations
+// that are not in an obstacle, pp_window_fill.h — device-resident state):
 //   window_samples Space::rand_point for the window's iterations (seeded stream), Morton-sorted
 //                  (the first window of a batch; later ones come from nn_finalize) rrt.rs:139-146
 //   window_kernel  workgroups 1..: the NN screen, K samples x N tree nodes, f32 SoA, expanded form
@@ -27,6 +28,7 @@
 #include <cstdlib>
 
 #include "pp_kernels.h"
+#include "pp_window_fill.h"
 
 // check_finish_kernel's register budget needs the polygon S classes as a call (as its cf_prep).
 // It is their only caller in this unit, and the inliner folds the last use of a local function
@@ -101,9 +103,12 @@ __device__ __forceinline__ float scan_d2(float qx, float qy, float nx, float ny)
     return __builtin_fmaf(dy, dy, dx * dx);
 }
 
-// window_samples: Space::rand_point for the iterations [start, start + W) of a window
-// (rrt.rs:139-146, seeded: Q7 — x = draw 2*it, y = draw 2*it + 1), W = min(K, target - start),
-// and a counting sort of the samples by the Morton index of their cell in a 16 x 16 grid over the
+// window_samples: Space::rand_point for the iterations [start, start + span) of a window
+// (rrt.rs:139-146, seeded: Q7 — x = draw 2*it, y = draw 2*it + 1).  The draws in an obstacle (the
+// pre-test) are settled here and take no sample id: the window's W <= min(K, kdyn) samples are its
+// live draws in iteration order, sample id drawn at iteration start + iter_off[id], and the window
+// spans up to twice as many iterations (pp_window_fill.h).  Then
+// a counting sort of the samples by the Morton index of their cell in a 16 x 16 grid over the
 // sampling box: perm[pos] = sample, so a screen block of 256 consecutive sorted samples is
 // spatially compact (the expanded screen's precision).  Within a cell the order is arbitrary —
 // the results never depend on it (only which samples meet the exact rescan).
@@ -125,12 +130,15 @@ struct SamplesArgs {
     double* sq[2];    // sample -> |q - o|^2 about its block's centre (f64, exact)
     int* ipos[2];     // sample -> sorted position (the screen's partials are stored by position)
     const SceneDev* scp = nullptr;       // the scene in device memory (point_blocked)
-    unsigned char* blk[2] = {nullptr, nullptr};  // sample -> its point lies in an obstacle
+    int pretest = 0;                     // draws in an obstacle are settled by samples_role
+    int* iter_off[2] = {nullptr, nullptr};  // sample -> its iteration's offset in the window
     // caller-drawn samples (pp_rrt_extend_samples): iteration it's sample is (hsx, hsy)[it -
-    // hs_base] instead of the seeded stream (null: the stream)
+    // hs_base] instead of the seeded stream (null: the stream); hok: the per-iteration verdicts
+    // (a draw in an obstacle: rejected, whichever window it falls in)
     const double* hsx = nullptr;
     const double* hsy = nullptr;
     int64_t hs_base = 0;
+    unsigned char* hok = nullptr;
 };
 
 // Space::rand_point of iteration itj (rrt.rs:139-146): the seeded stream (Q7: x = draw 2 it,
@@ -155,35 +163,39 @@ __device__ inline int morton16(int x, int y) {
 }
 
 // LDS of samples_role: the Morton histogram, each sample's cell, the sorted window's sample ids,
-// the count of samples in an obstacle
-constexpr int kSamplesLds = 256 * 4 + kMaxWindow + kMaxWindow * 4 + 16 + kMaxWindow;
+// each sample's iteration offset, the draw rounds' counters and per-wave live counts
+constexpr int kSamplesLds = 256 * 4 + kMaxWindow + kMaxWindow * 4 + 16 + 2 * 64 * 4 + kMaxWindow * 2;
 
+// (blockDim.x == 1024: both callers)
 __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t start,
                              char* smem) {
     int* s_hist = reinterpret_cast<int*>(smem);                  // [256]
     unsigned char* s_cell = reinterpret_cast<unsigned char*>(s_hist + 256);  // [K]
     int* s_j = reinterpret_cast<int*>(smem + 256 * 4 + kMaxWindow);  // [K] sorted position -> sample
-    int* s_nb = s_j + kMaxWindow;  // samples in an obstacle (sorted after the screened ones)
-    unsigned char* s_bk = reinterpret_cast<unsigned char*>(s_nb + 4);  // [K] sample in an obstacle
+    // [0] live draws so far, [1] the offset of live draw Kw (the next window's first), [2] a
+    // round's live draws
+    int* s_nb = s_j + kMaxWindow;
+    int* s_wt = s_nb + 4;   // [64] a round's live draws per (pass, wave)
+    int* s_wo = s_wt + 64;  // [64] their exclusive prefix
+    unsigned short* s_io = reinterpret_cast<unsigned short*>(s_wo + 64);  // [K] sample -> offset
+    static_assert(2 * kMaxWindow <= 65536, "samples_role: a window's offsets fit 16 bits");
     const int tid = threadIdx.x, NT = blockDim.x;
+    const int lane = tid & 63, wv = tid >> 6;
     const int64_t rem = g.target - start;
     // the adaptive window (kdyn, set by the commits; results never depend on the window size)
     const int Kw = st->kdyn > 0 ? min(g.K, st->kdyn) : g.K;
-    const int W = (rem <= 0 || st->error) ? 0 : (rem < Kw ? (int)rem : Kw);
-    if (tid == 0) {
-        st->Wp[np] = W;
-        st->wsp[np] = start;
-    }
     for (int i = tid; i < 256; i += NT) s_hist[i] = 0;
-    if (tid == 0) *s_nb = 0;
-    __syncthreads();
+    if (tid == 0) {
+        s_nb[0] = 0;
+        s_nb[1] = 0;
+    }
     const double fx = 16.0 / (g.maxx - g.minx), fy = 16.0 / (g.maxy - g.miny);
-    // (kU samples per thread per pass: their pre-test loads are in flight together)
+    // (kU draws per thread per round: their pre-test loads are in flight together)
     constexpr int kU = 4;
-    const bool pre = g.blk[np] != nullptr;
     // the pre-test's scene fields, loaded once (through the pointer they would be reloaded after
     // every store below, which the compiler cannot prove disjoint)
     SceneDev scl{};
+    bool pre = g.pretest != 0;
     if (pre) {
         scl.bits = g.scp->bits;
         scl.bw = g.scp->bw;
@@ -212,47 +224,101 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
         scl.gnx = g.scp->gnx;
         scl.gny = g.scp->gny;
     }
-    for (int j0 = tid; j0 < W; j0 += NT * kU) {
-        double xs[kU], ys[kU];
-        bool bks[kU];
+    // (a scene without a pre-test — polygons, no discs: every draw is live and the window is its
+    // Kw iterations)
+    pre = pre && (scl.bits || (scl.m > 0 && scl.ne == 0 && scl.nbv == 0));
+    const int C = st->error ? 0 : window_fill_cap(Kw, rem, pre);
+    // sample j, drawn at offset i of the window
+    auto place = [&](int j, int i, double x, double y) {
+        g.wsx[np][j] = x;
+        g.wsy[np][j] = y;
+        g.wsx32[np][j] = (float)x;
+        g.wsy32[np][j] = (float)y;
+        g.iter_off[np][j] = i;
+        s_io[j] = (unsigned short)i;
+        const int cx = min(max((int)((x - g.minx) * fx), 0), 15);  // == sample_cell
+        const int cy = min(max((int)((y - g.miny) * fy), 0), 15);
+        const int cell = morton16(cx, cy);
+        s_cell[j] = (unsigned char)cell;
+        atomicAdd(&s_hist[cell], 1);
+    };
+    __syncthreads();
+    if (!pre) {  // every draw is live: sample j is draw j, one pass
+        for (int j0 = tid; j0 < C; j0 += NT * kU) {
+            double xs[kU], ys[kU];
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int j = j0 + u * NT;
-            xs[u] = ys[u] = 0.0;
-            if (j < W) {
-                draw_sample(g, (uint64_t)(start + j), xs[u], ys[u]);
+            for (int u = 0; u < kU; ++u) {
+                const int j = j0 + u * NT;
+                xs[u] = ys[u] = 0.0;
+                if (j < C) draw_sample(g, (uint64_t)(start + j), xs[u], ys[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int j = j0 + u * NT;
+                if (j < C) place(j, j, xs[u], ys[u]);
             }
         }
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-            bks[u] = pre && j0 + u * NT < W && point_blocked<false, kSceneAny>(scl, xs[u], ys[u]);
+        if (tid == 0) s_nb[0] = C;
+    }
+    // the pre-test's draws, in rounds: draw i of the window is iteration start + i; a wave takes
+    // 64 consecutive draws, so a ballot and the waves' prefix give every live draw its id in
+    // iteration order.  A round is kU draws per thread, kept in registers from the pre-test to
+    // the stores, then half as many.  (One longer round with the masks in LDS and the draws made
+    // again for the stores was slower: 27.7 against 26.5 us for the benched window.)
+    for (int drawn = 0; pre;) {
+        __syncthreads();
+        const int live0 = s_nb[0];
+        if (!window_fill_more(Kw, C, drawn, live0)) break;
+        const int end = window_fill_round_end(C, drawn, NT * kU, NT * kU / 2);
+        double xs[kU], ys[kU];
+        uint64_t mk[kU];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            const int j = j0 + u * NT;
-            const bool valid = j < W;
-            // a sample in an obstacle needs no nearest node and is nobody's candidate parent: it
-            // is sorted after the screened samples, out of the screen and the pair grid (counted
-            // per wave: one LDS atomic instead of one per sample on a single address)
-            const uint64_t mb = __ballot(valid && bks[u]);
-            if ((__lane_id()) == 0 && mb) atomicAdd(s_nb, (int)__popcll(mb));
-            if (!valid) continue;
-            const double x = xs[u], y = ys[u];
-            g.wsx[np][j] = x;
-            g.wsy[np][j] = y;
-            g.wsx32[np][j] = (float)x;
-            g.wsy32[np][j] = (float)y;
-            if (pre) g.blk[np][j] = bks[u] ? 1 : 0;
-            s_bk[j] = bks[u] ? 1 : 0;
-            const int cx = min(max((int)((x - g.minx) * fx), 0), 15);  // == sample_cell
-            const int cy = min(max((int)((y - g.miny) * fy), 0), 15);
-            const int cell = morton16(cx, cy);
-            s_cell[j] = (unsigned char)cell;
-            if (!bks[u]) atomicAdd(&s_hist[cell], 1);
+            const int i = drawn + u * NT + tid;
+            xs[u] = ys[u] = 0.0;
+            if (i < end) draw_sample(g, (uint64_t)(start + i), xs[u], ys[u]);
         }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const bool in = drawn + u * NT + tid < end;
+            const bool lv = in && !point_blocked<false, kSceneAny>(scl, xs[u], ys[u]);
+            mk[u] = __ballot(lv);
+            if (lane == 0) s_wt[u * (1024 / 64) + wv] = (int)__popcll(mk[u]);
+        }
+        __syncthreads();
+        if (tid < 64) {
+            const int v = s_wt[tid];
+            const int x = wave_incl_scan(v);
+            s_wo[tid] = x - v;
+            if (tid == 63) s_nb[2] = x;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = drawn + u * NT + tid;
+            if (i >= end) continue;
+            if (!((mk[u] >> lane) & 1)) {
+                // in an obstacle: rejected whatever its parent, whichever window it falls in
+                if (g.hok) g.hok[start + i - g.hs_base] = 0;
+                continue;
+            }
+            const int j = live0 + s_wo[u * (1024 / 64) + wv] + (int)__popcll(mk[u] & ((1ull << lane) - 1));
+            if (j == Kw) s_nb[1] = i;
+            if (j < Kw) place(j, i, xs[u], ys[u]);
+        }
+        __syncthreads();
+        if (tid == 0) s_nb[0] = live0 + s_nb[2];
+        drawn = end;
     }
     __syncthreads();
-    const int Ws = W - *s_nb;  // screened samples: sorted positions [0, Ws)
-    if (tid == 0) st->Wsp[np] = Ws;
+    const WindowFill wf = window_fill_close(Kw, C, s_nb[0], s_nb[1]);
+    const int W = wf.W, Ws = W;  // every sample is screened: sorted positions [0, W)
+    if (tid == 0) {
+        st->Wp[np] = W;
+        st->Wsp[np] = W;
+        st->span[np] = wf.span;
+        st->wsp[np] = start;
+    }
     // the screen's blocks of rows for Ws samples (the tiling's split; its chunks are the
     // screen's and nn_finalize's business)
     const int R = screen_rows(Ws), nqb = (R + kQPL - 1) / kQPL;
@@ -274,33 +340,14 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
     }
     __syncthreads();
     for (int i = tid; i < 256; i += NT) g.cofs[np][i] = s_hist[i];
-    if (tid == 0) {
-        g.cofs[np][256] = Ws;
-        *s_nb = Ws;  // (now the next free position of the blocked bucket)
-    }
+    if (tid == 0) g.cofs[np][256] = Ws;
     __syncthreads();  // the cell starts are read before the scatter advances them
-    for (int j0 = tid - (tid & 63); j0 < W; j0 += NT) {  // whole waves (the ballot below)
-        const int j = j0 + (tid & 63);
-        const bool bk = j < W && s_bk[j];
-        // the blocked bucket: a wave's blocked samples take consecutive positions (one atomic)
-        const uint64_t mb = __ballot(bk);
-        int base = 0;
-        if ((tid & 63) == 0 && mb) base = atomicAdd(s_nb, (int)__popcll(mb));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (j >= W) continue;
-        s_j[bk ? base + (int)__popcll(mb & ((1ull << (tid & 63)) - 1)) : atomicAdd(&s_hist[s_cell[j]], 1)] = j;
-    }
+    for (int j = tid; j < W; j += NT) s_j[atomicAdd(&s_hist[s_cell[j]], 1)] = j;
     __syncthreads();
-    // the screen's blocks of sorted samples (rows of 64, split as the tiling's): the sorted window (coalesced; the
-    // coordinates drawn again from the stream, bit-identical), the centre o of the block's
+    // the screen's blocks of sorted samples (rows of 64, split as the tiling's): the sorted window
+    // (coalesced; the coordinates drawn again from the stream, bit-identical), the centre o of the block's
     // bounding box (f32) and every sample's |q - o|^2 in f64 — (q - o) rounded to f32 per axis,
     // the screen's own operands, squared exactly (nn_finalize adds it back to the screen values)
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int pos = Ws + tid; pos < W; pos += NT) {  // the blocked bucket: perm / ipos only
-        const int j = s_j[pos];
-        g.perm[np][pos] = j;
-        g.ipos[np][j] = pos;
-    }
     // every thread takes sorted positions tid, tid + NT, ... (a wave: 64 consecutive positions,
     // inside one block): the coordinates again from the stream, the position's stores, and the
     // wave's f32 bounding box into LDS slot pos / 64 (s_hist is free by now); then one thread per
@@ -312,7 +359,6 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
     // dead after the scatter
     float* s_bb = reinterpret_cast<float*>(s_hist);
     int* s_rb = reinterpret_cast<int*>(s_bb + 4 * (kMaxWindow / 64) + 2 * (kMaxWindow / kQPB));  // [rows]
-    (void)wv;
     __syncthreads();  // (s_hist's last readers: the scatter above)
     constexpr int kMaxK = 4;  // positions per thread: both callers run 1024 threads
     static_assert(kMaxWindow <= 1024 * kMaxK, "samples_role: positions per thread");
@@ -326,7 +372,7 @@ __device__ void samples_role(DevState* st, const SamplesArgs& g, int np, int64_t
         const bool in = pos < Ws;
         if (in) {
             const int j = s_j[pos];
-            draw_sample(g, (uint64_t)(start + j), xs[k], ys[k]);
+            draw_sample(g, (uint64_t)(start + s_io[j]), xs[k], ys[k]);
             g.perm[np][pos] = j;
             g.ipos[np][j] = pos;
             g.sxy[np][pos] = make_float2((float)xs[k], (float)ys[k]);
@@ -903,7 +949,7 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
     double* __restrict__ out_d2, double* __restrict__ out_pose, PairGrid pg,
     int* __restrict__ cand_cnt, CandEntry* __restrict__ cand,
     int* __restrict__ pend, const double* __restrict__ sq, const int* __restrict__ ipos,
-    SamplesArgs gen, int gen_next, const unsigned char* __restrict__ blk) {
+    SamplesArgs gen, int gen_next) {
     __shared__ double s_nd2[kFinSamples];  // exact snapshot NN d2 of each sample
     __shared__ int s_pc[kFinSamples];      // pair search: nearer window samples found
     __shared__ int s_pi[kFinSamples][kCandCap];
@@ -927,7 +973,7 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
         // workgroup 0 advances it_spec only when this window is not voided).  Off the critical
         // path: steer_prep and steer_walk of this window run before the next screen.
         __shared__ __attribute__((aligned(16))) char s_gen[kSamplesLds];
-        const int64_t start = voided ? st->it_spec : st->wsp[p] + st->Wp[p];
+        const int64_t start = voided ? st->it_spec : st->wsp[p] + st->span[p];
         samples_role(st, gen, 1 - p, start, s_gen);
         FS(9)
         return;
@@ -936,18 +982,17 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
     const int ns = st->nsp[p], n = st->n;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         st->W = W;
+        // (the iterations the window spans: its samples and the draws in an obstacle between them)
+        st->span_cur = voided ? 0 : st->span[p];
         st->n_scan = n;
-        if (!voided) st->it_spec = st->wsp[p] + W;
+        if (!voided) st->it_spec = st->wsp[p] + st->span[p];
     }
     const int q0 = (int)blockIdx.x * kFinSamples;
     if (q0 >= W) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = q0 + wave;
-    // a sample in an obstacle is rejected whatever its parent: no nearest node, no pair list, and
-    // it is nobody's candidate parent (samples_role's point_blocked)
-    const bool qblk = blk && q < W && blk[q];
-    const bool in = q < W && !qblk;
+    const bool in = q < W;
     const int D = n - ns, Dl = min(D, kFinDelta);  // appended nodes (staged: the first kFinDelta)
     for (int k = tid; k < Dl; k += kFinThreads) s_dn[k] = make_float2(x32[ns + k], y32[ns + k]);
     if (tid < kMaxWindow / 64) {
@@ -1158,7 +1203,7 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
         // wave w: sample j = q0 + w against the window samples i < j of the Morton cells its
         // disc of radius sqrt(D2) touches (the binning is monotone, so the cells are a superset)
         const int j = q0 + wave;
-        if (j < W && !qblk) {
+        if (j < W) {
             const double xj = qx[j], yj = qy[j];
             const float xjf = (float)xj, yjf = (float)yj;
             const double D2 = s_nd2[wave];
@@ -1171,9 +1216,8 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
                 for (int cx = cx0; cx <= cx1; ++cx) {
                     const int m = morton16(cx, cy);
                     const int a1 = pg.cofs[m + 1];
-                    // (the cells list only the screened samples, none in an obstacle; a
-                    // candidate's index and f64 coordinates are read by sorted position, beside
-                    // its f32 prefilter, not through perm)
+                    // (a candidate's index and f64 coordinates are read by sorted position,
+                    // beside its f32 prefilter, not through perm)
                     for (int pos = pg.cofs[m] + lane; pos < a1; pos += 64) {
                         const float2 v = pg.sxy[pos];
                         const int ii = pg.perm[pos];
@@ -1216,10 +1260,6 @@ __global__ __launch_bounds__(kFinThreads, 8) void nn_finalize_kernel(
             cand[eb + k] = CandEntry{j, s_pi[lane][k], s_pd[lane][k], 0.0, -1, 0};
         if (cnt > 0) pend[pb] = j;
         if (lane == 0 && ov) atomicMin(&st->weff, q0 + (int)__builtin_ctzll(ov));
-        if (blk) {  // statistics (pp_stats.samples_blocked): one atomic per workgroup
-            const uint64_t bm = __ballot(jin && blk[j]);
-            if (lane == 0 && bm) atomicAdd((unsigned long long*)&st->blocked, (unsigned long long)__popcll(bm));
-        }
         FS(8)
     }
 }
@@ -1562,7 +1602,8 @@ __device__ __attribute__((always_inline)) inline void commit_role(
     const double* __restrict__ wsy, const int* __restrict__ nn_idx,
     const int* __restrict__ snap_status, const double* __restrict__ snap_yaw,
     const int* __restrict__ fin_par, int* __restrict__ cand_cnt, int W, int64_t void_next,
-    int64_t screened, const SampleRec& hrec, char* smem) {
+    int64_t screened, const SampleRec& hrec, const int* __restrict__ iter_off, int span,
+    char* smem) {
     constexpr int PER = kMaxWindow / NT;
     static_assert(PER % 4 == 0, "commit: whole int4 loads per thread");
     int* s_node = reinterpret_cast<int*>(smem);
@@ -1626,16 +1667,20 @@ __device__ __attribute__((always_inline)) inline void commit_role(
         for (int u = 0; u < PER; ++u) {
             const int j = j0 + u;
             if (j >= Weff) continue;
-            const int64_t r = it0 + j - hrec.base;
+            const int64_t r = it0 + iter_off[j] - hrec.base;
             if (hrec.ok) hrec.ok[r] = (unsigned char)(v[u] & 1);
             if (hrec.par) hrec.par[r] = (v[u] & kWinParent) ? s_node[fin_par[j]] : nn_idx[j];
             if (hrec.yaw) hrec.yaw[r] = snap_yaw[j];
         }
     }
     if (tid == 0) {
+        // the iterations committed: the whole span, or, cut at sample Weff, up to that sample's
+        // iteration (the draws in an obstacle before it were settled when they were drawn)
+        const int adv = Weff < W ? iter_off[Weff] : span;
         st->n = n0 + total;
-        st->it = it0 + Weff;
-        st->iterations += Weff;
+        st->it = it0 + adv;
+        st->iterations += adv;
+        st->blocked += adv - Weff;
         st->accepted += total;
         st->windows += 1;
         st->truncations += Weff < W;
@@ -1644,13 +1689,13 @@ __device__ __attribute__((always_inline)) inline void commit_role(
         // tree nodes it scanned (nodes past n_scan are nn_finalize's, a few per window)
         st->node_evals += screened;
         if (Weff < W) {
-            st->it_spec = it0 + Weff;
+            st->it_spec = it0 + adv;
             if (void_next >= 0) st->void_seq = void_next;
         }
         // adaptive window (a young tree: the window's samples are mostly nearer to each other than
         // to the tree, lists overflow and windows are cut): a cut window shrinks the next draws to
         // the power of two at or above where it stopped, a full one doubles them (<= K, clamped by
-        // the draws).  Only the speed depends on it: the results are those of one sample at a time.
+        // the draws).  kdyn counts samples, not iterations.  Only the speed depends on it: the results are those of one sample at a time.
         int kd = st->kdyn > 0 ? st->kdyn : kMaxWindow;
         if (Weff < W) {
             kd = kMinDynWindow;
@@ -1680,9 +1725,10 @@ __global__ __launch_bounds__(kScanThreads) void window_kernel(WinKArgs a) {
         DevState* st = a.st;
         if (a.resolve) {
             const int W = st->W;
-            if (W > 0) {
+            // (a window of draws in obstacles alone has no sample and still commits its span)
+            if (st->span_cur > 0) {
                 const int q = 1 - a.p;
-                if (!resolve_role<kWinRepair, kScanThreads>(st, a.sc, a.tr, a.wsx[q], a.wsy[q], a.nn_idx,
+                if (W > 0 && !resolve_role<kWinRepair, kScanThreads>(st, a.sc, a.tr, a.wsx[q], a.wsy[q], a.nn_idx,
                                                        a.cand_cnt, a.cand, a.pend, a.snap_status,
                                                        a.snap_yaw, a.fin_par, a.rs, a.lit_scratch,
                                                        W, smem)) {
@@ -1694,7 +1740,8 @@ __global__ __launch_bounds__(kScanThreads) void window_kernel(WinKArgs a) {
                 commit_role<kScanThreads>(st, a.tr, a.wsx[q], a.wsy[q], a.nn_idx, a.snap_status,
                                           a.snap_yaw, a.fin_par, a.cand_cnt, W,
                                           a.scan ? a.seq : -1,
-                                          (int64_t)st->Wsp[q] * st->nsp[q], a.hrec, smem);
+                                          (int64_t)st->Wsp[q] * st->nsp[q], a.hrec,
+                                          a.g.iter_off[q], st->span_cur, smem);
             }
         }
         if (threadIdx.x == 0) {  // the screened window's counters start at zero
@@ -1731,7 +1778,8 @@ __global__ __launch_bounds__(kResolveThreads) void resolve_tail_kernel(WinKArgs 
     __syncthreads();
     commit_role<kResolveThreads>(st, a.tr, a.wsx[q], a.wsy[q], a.nn_idx, a.snap_status,
                                  a.snap_yaw, a.fin_par, a.cand_cnt, W, a.scan ? a.seq : -1,
-                                 (int64_t)st->Wsp[q] * st->nsp[q], a.hrec, smem);
+                                 (int64_t)st->Wsp[q] * st->nsp[q], a.hrec, a.g.iter_off[q],
+                                 st->span_cur, smem);
     if (threadIdx.x == 0) {
         st->resolve_bail = 0;
         st->flag_count = 0;
@@ -4601,12 +4649,14 @@ SamplesArgs samples_args(const WindowArgs& a) {
         g.ob[q] = a.ob + (size_t)q * (kMaxWindow / kQPB);
         g.sq[q] = a.sq + (size_t)q * a.Kcap;
         g.ipos[q] = a.ipos + (size_t)q * a.Kcap;
-        g.blk[q] = a.blk ? a.blk + (size_t)q * a.Kcap : nullptr;
+        g.iter_off[q] = a.iter_off + (size_t)q * a.Kcap;
     }
     g.scp = a.scp;
     g.hsx = a.hsx;
     g.hsy = a.hsy;
     g.hs_base = a.hrec.base;
+    g.hok = a.hrec.ok;
+    g.pretest = a.pretest;
     return g;
 }
 PairGrid pair_grid(const SamplesArgs& g, int p, double eps_coord) {
@@ -4693,12 +4743,12 @@ hipError_t launch_window(hipStream_t s, const WindowArgs& a, hipEvent_t* ev, int
         a.st, p, seq, wk.chunks, a.pbest, a.psecond, a.pidx, a.Kcap, wsx, wsy, a.tr.x32, a.tr.y32,
         a.tr.x, a.tr.y, a.tr.yaw, a.eps_coord, a.nn_idx, a.nn_d2, a.snap_pose,
         pair_grid(wk.g, p, a.eps_coord), a.cand_cnt, a.cand, a.pend, wk.sq[p], wk.g.ipos[p], wk.g,
-        1, wk.g.blk[p]);
+        1);
     if (ev) (void)hipEventRecord(ev[2], s);
     // snapshot and candidate tasks together: prep covers 2K tasks per pass, walk 4 per workgroup
     const int prep_blocks = (2 * K + kPrepThreads / 8 - 1) / (kPrepThreads / 8);
     launch_prep_window(s, prep_blocks, a.st, a.sc, wsx, wsy, a.snap_pose, a.cand, a.rec,
-                       a.snap_yaw, wk.g.blk[p]);
+                       a.snap_yaw);
     if (ev) (void)hipEventRecord(ev[3], s);
     // snapshot tasks plus the usual few candidate tasks in one round of waves
     const int nwg = walk_blocks(K + K / 4, walk_grid_limit(kWalkWindow, a.sc));
@@ -4722,7 +4772,7 @@ hipError_t launch_nearest(hipStream_t s, const WindowArgs& a) {
     nn_finalize_kernel<<<(K + kFinSamples - 1) / kFinSamples, kFinThreads, 0, s>>>(
         a.st, 0, 0, wk.chunks, a.pbest, a.psecond, a.pidx, a.Kcap, a.wsx, a.wsy, a.tr.x32,
         a.tr.y32, a.tr.x, a.tr.y, a.tr.yaw, a.eps_coord, a.nn_idx, a.nn_d2, nullptr, PairGrid{},
-        nullptr, nullptr, nullptr, nullptr, nullptr, wk.g, 0, nullptr);
+        nullptr, nullptr, nullptr, nullptr, nullptr, wk.g, 0);
     return hipGetLastError();
 }
 

@@ -52,7 +52,7 @@ int ensure_window(pp_ctx* c, int K) {
     PP_HIP(c->rrt.r_rep.reserve(k));
     PP_HIP(c->rrt.pend.reserve(k));
     PP_HIP(c->rrt.fin_par.reserve(k));
-    PP_HIP(c->rrt.blk.reserve(2 * k));
+    PP_HIP(c->rrt.iter_off.reserve(2 * k));
     PP_HIP(hipMemsetAsync(c->rrt.cand_cnt.p, 0, k * sizeof(int), c->stream));
     PP_HIP(c->rrt.r_repyaw.reserve(k));
     PP_HIP(c->rrt.tasks.reserve(k));
@@ -161,6 +161,7 @@ int pp_rrt_new(pp_ctx* ctx, double sx, double sy, double syaw, double gx, double
     PP_HIP(hipMemcpy(ctx->rrt.d_state.p, &s, sizeof(DevState), hipMemcpyHostToDevice));
     ctx->rrt.h_state.p[0] = s;
     ctx->rrt.n = 1;
+    ctx->rrt.blocked_share = -1.0;
     ctx->rrt.valid = true;
     return PP_OK;
 }
@@ -226,12 +227,29 @@ int rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted, const Samp
         const SceneDev sd = ctx->scene_dev();
         PP_HIP(hipMemcpy(ctx->rrt.d_scene.p, &sd, sizeof sd, hipMemcpyHostToDevice));
     }
+    // the pre-test settles the draws in an obstacle where they are drawn: a window holds Kd live
+    // samples and spans more iterations (pp_window_fill.h)
+    const bool pretest = !ctx->scene.polygons() && (!src || src->pretest);
     while (ctx->rrt.it < target) {
         const int K = ctx->rrt.K;
-        // windows draw min(K, kdyn) samples (the device adapts kdyn): enough windows for that
+        // windows hold min(K, kdyn) samples (the device adapts kdyn): enough windows for the live
+        // draws expected of the remaining iterations — their share from the previous batch's
+        // counters, else from the pre-test's set cells — three standard deviations up; never
+        // more than one per Kd iterations nor fewer than one per 2 Kd (a window's bounds).  A
+        // window past the target is four empty launches, a shortfall another batch (this loop).
         const int64_t Kd = std::max(1, std::min(K, ctx->rrt.h_state.p[0].kdyn > 0 ? ctx->rrt.h_state.p[0].kdyn : K));
-        const int64_t nw64 = std::min<int64_t>((target - ctx->rrt.it + Kd - 1) / Kd, kMaxBatch);
+        const int64_t rem = target - ctx->rrt.it;
+        const double share = !pretest ? 0.0
+                             : ctx->rrt.blocked_share >= 0.0 ? ctx->rrt.blocked_share
+                                                             : ctx->scene.blocked_share;
+        const double live = (double)rem * (1.0 - share) +
+                            3.0 * std::sqrt((double)rem * share * (1.0 - share));
+        int64_t nw64 = (int64_t)std::ceil(live / (double)Kd);
+        nw64 = std::max(nw64, (rem + 2 * Kd - 1) / (2 * Kd));
+        nw64 = std::min(nw64, (rem + Kd - 1) / Kd);
+        nw64 = std::min<int64_t>(std::max<int64_t>(nw64, 1), kMaxBatch);
         const int nw = (int)nw64;
+        const int64_t it_before = ctx->rrt.it, blocked_before = ctx->rrt.h_state.p[0].blocked;
         if ((r = ensure_tree(ctx, ctx->rrt.n + (int64_t)nw * K))) return r;
         WindowArgs a = ctx->rrt.window_args(ctx->scene_dev(), ctx->prof.points(), ctx->rrt.d_state.p);
         a.K = K;
@@ -241,7 +259,7 @@ int rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted, const Samp
             a.hsx = src->x;
             a.hsy = src->y;
             a.hrec = src->rec;
-            if (!src->pretest) a.blk = nullptr;
+            if (!src->pretest) a.pretest = 0;
         }
         if (ctx->prof.on && (r = ensure_events(ctx, 5 * (size_t)nw))) return r;
         const int64_t windows_before = ctx->rrt.h_state.p[0].windows;
@@ -273,6 +291,8 @@ int rrt_extend_impl(pp_ctx* ctx, int64_t n_iter, int64_t* n_accepted, const Samp
         }
         ctx->rrt.it = s.it;
         ctx->rrt.n = s.n;
+        if (pretest && s.it > it_before && s.blocked >= blocked_before)
+            ctx->rrt.blocked_share = (double)(s.blocked - blocked_before) / (double)(s.it - it_before);
 #ifdef PP_FIN_STAMPS
         dump_fin_stamps(ctx->rrt.n, nw);
 #endif

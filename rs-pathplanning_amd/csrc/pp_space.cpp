@@ -73,6 +73,7 @@ void install_scene(pp_ctx* ctx, double minx, double maxx, double miny, double ma
     s.max_steer = max_steer;
     s.m = m;
     s.has_grid = false;
+    s.blocked_share = 0.0;
     s.valid = true;
     // the trees stay on the device: pp_rrt_revalidate / pp_batch_revalidate carry them over
     ctx->rrt.stale |= ctx->rrt.valid;
@@ -124,6 +125,7 @@ int pp_space_new(pp_ctx* ctx, double x0, double y0, double x1, double y1, double
         (rc = upload(s.d_r2, ds.r2.data(), mm)) || (rc = upload(s.d_rcull, ds.rcull.data(), mm)))
         return rc;
     clear_polygons(s);
+    double ib_share = 0.0;
     {  // the inside bitmap: 2048^2 cells (512 KB, L2-resident)
         const scene::InsideBits ib =
             scene::inside_bitmap(ds.minx, ds.maxx, ds.miny, ds.maxy, cx, cy, ds.r2, kInsideCells);
@@ -135,10 +137,17 @@ int pp_space_new(pp_ctx* ctx, double x0, double y0, double x1, double y1, double
             s.ibx0 = ib.x0;
             s.iby0 = ib.y0;
             s.ibinv = ib.inv;
+            // set cells over the cells of the sampling box (the bitmap is square, the box may not be)
+            const double nx = std::min((double)ib.n, std::ceil((ds.maxx - ds.minx) * ib.inv));
+            const double ny = std::min((double)ib.n, std::ceil((ds.maxy - ds.miny) * ib.inv));
+            uint64_t set = 0;
+            for (uint32_t w : ib.bits) set += (uint64_t)__builtin_popcount(w);
+            if (nx >= 1.0 && ny >= 1.0) ib_share = std::min(1.0, (double)set / (nx * ny));
         }
     }
     install_scene(ctx, ds.minx, ds.maxx, ds.miny, ds.maxy, ds.items.mx, robot_width, robot_height,
                   max_steer, m);
+    s.blocked_share = ib_share;
     return PP_OK;
 }
 
@@ -205,6 +214,11 @@ int pp_space_set_grid(pp_ctx* ctx, const uint32_t* bits, int w, int h, double x0
         PP_HIP(hipMemcpy(s.d_gimg.p, img.data(), img_bytes, hipMemcpyHostToDevice));
     }
     s.has_grid = true;
+    {
+        uint64_t set = 0;
+        for (size_t i = 0; i < n; ++i) set += (uint64_t)__builtin_popcount(bits[i]);
+        s.blocked_share = std::min(1.0, (double)set / ((double)w * (double)h));
+    }
     ctx->rrt.stale |= ctx->rrt.valid;
     ctx->rrt.valid = false;  // the planner's Space changed (rrt.rs:342)
     return PP_OK;

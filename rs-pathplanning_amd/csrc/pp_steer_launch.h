@@ -52,8 +52,7 @@ void launch_walk(WalkProfile p, hipStream_t s, int blocks, DevState* st, const S
 // steer_prep_kernel over a window's snapshot and candidate tasks
 void launch_prep_window(hipStream_t s, int blocks, const DevState* st, const SceneDev& sc,
                         const double* wsx, const double* wsy, const double* snap_pose,
-                        CandEntry* cand, PrepRec* rec, double* snap_yaw,
-                        const unsigned char* blk);
+                        CandEntry* cand, PrepRec* rec, double* snap_yaw);
 // ... and over explicit (child, parent pose) tasks: yaw[t] the child's heading, cost (optional)
 // the edge's Dubins cost, ext (optional) RRT*'s own-yaw children and cull limits
 void launch_prep_tasks(hipStream_t s, int blocks, const DevState* st, const SceneDev& sc,

@@ -125,19 +125,22 @@ struct DevState {
     int n_scan;      // tree nodes the next window's scan covers (nodes past it: nn_finalize)
     int64_t it_spec; // first iteration of the next window to scan
     int64_t wsp[2];  // per parity: first iteration of the window the scan generated
-    int Wp[2];       // per parity: its sample count
+    int Wp[2];       // per parity: its sample count (the live draws: none in an obstacle)
+    int span[2];     // per parity: the iterations it spans (>= Wp: pp_window_fill.h)
+    int span_cur;    // the current window's span (0: nothing left to do / void window)
     int nsp[2];      // per parity: tree nodes its scan covered
-    int Wsp[2];      // per parity: samples the screen covers (the window's samples not in an
-                     // obstacle: sorted positions [0, Wsp); samples_role)
+    int Wsp[2];      // per parity: samples the screen covers (all of the window's, == Wp: sorted
+                     // positions [0, Wsp); samples_role)
                      // — and with them the screen's tiling (pp_screen_geom.h: a table by their
                      // rows of 64)
     int64_t void_seq;  // window sequence number voided by a truncated predecessor (-1: none)
     int resolve_bail;  // the window kernel's resolve needed a repair: resolve_tail_kernel redoes it
-    int kdyn;          // adaptive window: samples drawn per window (<= K; the commit adapts it)
+    int kdyn;          // adaptive window: samples per window (<= K; the commit adapts it)
     // statistics (pp_stats)
     int64_t iterations, accepted, windows, truncations, repair_rounds, repairs, literal_repairs,
         nn_flagged, node_evals;
-    int64_t blocked;  // samples in an obstacle (point_blocked): rejected without steer or pair list
+    int64_t blocked;  // committed iterations whose draw lies in an obstacle (point_blocked):
+                      // rejected where they are drawn, without a sample id
     // the query batch's active-task list (round 5): steer_prep / steer_walk run over i < W with the
     // compacted task i (its record at i) and store its yaw at slot alist[i], its verdict in list
     // order (MqDev::lstat); null: task i is slot i (the window pipeline, RRT*, the steer rounds)

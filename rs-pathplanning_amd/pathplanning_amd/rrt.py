@@ -197,8 +197,10 @@ class RRT:  # rrt.rs:325-620
     """``RRT::new(start, start_yaw, goal, goal_yaw, max_iter, step_size, space)`` (rrt.rs:335).
 
     Extra keyword arguments: ``seed`` (sampling stream), ``device`` (GPU ordinal), ``window``
-    (candidates evaluated per speculative GPU batch; results do not depend on it), ``capacity``
-    (initial node capacity, grown on demand)."""
+    (samples screened per speculative GPU window; an iteration whose sample lies in an obstacle is
+    rejected where it is drawn and takes none of them, so a window spans up to twice as many
+    iterations; results do not depend on it), ``capacity`` (initial node capacity, grown on
+    demand)."""
 
     def __init__(self, start, start_yaw, goal, goal_yaw, max_iter, step_size, space: Space,
                  seed: int = 0, device: int = 0, window: int = 4096, capacity: int = 1 << 16,
