@@ -42,7 +42,9 @@ extern "C" {
  * 5 (+): pp_star_repair added (dropped subtrees re-attached under kept nodes after a scene
  *    change), nothing else changed
  * 5 (+): PP_COORD_MAX, pp_coord_check and pp_sincos_small_batch added; positions above
- *    PP_COORD_MAX are now PP_ERR_INVALID_ARGUMENT, nothing else changed */
+ *    PP_COORD_MAX are now PP_ERR_INVALID_ARGUMENT, nothing else changed
+ * 5 (+): PP_STAR_FOCUS_DRAWS, pp_star_set_focus and pp_star_get_focus added (focused sampling of
+ *    the RRT* batch); a batch that never sets a focus runs as before bit for bit */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -420,6 +422,33 @@ int pp_star_state(pp_ctx* ctx, int32_t* n_nodes, int64_t* iterations, int64_t* n
 /* one query's tree (root first): coordinates, yaw, parent (-1 root) and node cost (root 0) */
 int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* yaw,
                         int32_t* parent, double* cost, int64_t cap, int64_t* n);
+/* Focused sampling (build-defined, DESIGN.md §3.7 "Focused sampling"; CPU restatement
+ * tests/star_focus_ref.py): Informed RRT* as a rejection filter on the same counter RNG.  Every
+ * query carries a focus point (fx, fy), a bound L in length units (finite and > 0, or +inf: no
+ * focus) and a counter `skipped` of rejected draws; pp_star_new sets L = +inf and skipped = 0.
+ * Draw d of a query is the point (gen_range(seed, 2d, minx, maxx), gen_range(seed, 2d + 1, miny,
+ * maxy)), and (x0, y0) is its root's stored point.  Iteration `it` of a query:
+ *   L = +inf:  the sample is draw it + skipped, then the iteration of pp_star_new's comment (with
+ *              skipped = 0: that iteration exactly).
+ *   L finite:  for j = 0 .. PP_STAR_FOCUS_DRAWS - 1 the draw it + skipped + j is in the set iff
+ *              sqrt((x-x0)*(x-x0) + (y-y0)*(y-y0)) + sqrt((x-fx)*(x-fx) + (y-fy)*(y-fy)) < L
+ *              (f64, uncontracted, correctly rounded square roots; the raw sample, before Steer).
+ *              At the first j in the set skipped += j and the iteration runs with that sample.
+ *              With none, skipped += PP_STAR_FOCUS_DRAWS - 1 and the iteration ends: no nearest
+ *              node, no insert, no rewire, no node evaluations.
+ * Either way it += 1: a step is still one iteration per query, and max_iter, the tree capacity
+ * and the k schedule are untouched; only the draw counter runs ahead.  An empty set (L at most the
+ * distance between the root and the focus) is legal: every iteration then rejects all its draws.
+ * pp_star_revalidate, pp_star_repair, pp_space_*, pp_star_plan and pp_star_paths leave the focus
+ * and skipped alone; only pp_star_set_focus and pp_star_new change them. */
+#define PP_STAR_FOCUS_DRAWS 1024
+/* fxy: q rows (fx, fy); bound: q values L.  Both NULL: every query's focus is cleared (L = +inf),
+ * skipped is kept.  PP_ERR_INVALID_ARGUMENT for exactly one NULL, for a bound that is NaN, <= 0 or
+ * -inf, and for a focus row that fails pp_coord_check; a failed call leaves the focus as it was.
+ * PP_ERR_STATE without an RRT* batch. */
+int pp_star_set_focus(pp_ctx* ctx, const double* fxy, const double* bound);
+/* fxy (2q), bound (q), skipped (q int64); each may be NULL */
+int pp_star_get_focus(pp_ctx* ctx, double* fxy, double* bound, int64_t* skipped);
 /* Re-verify every query's tree of the RRT* batch against the context's current Space and drop
  * what no longer holds (build-defined; CPU restatement
  * tests/star_revalidate_ref.py).  The edge of node i > 0 is RRT*'s feasible edge (§3.7) from its

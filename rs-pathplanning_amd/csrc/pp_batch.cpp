@@ -2,6 +2,8 @@
 // (pp_batch_*) and the RRT* batch (pp_star_*) on top of it.
 #include "pp_ctx.h"
 
+#include <limits>
+
 using namespace ppamd;
 
 int Forest::init(pp_ctx* c, int q, int64_t max_iter_, double step_, const double* starts,
@@ -296,6 +298,9 @@ StarArgs ppamd::star_args(pp_ctx* c) {
     StarArgs a;
     StarDev& d = a.sd;
     d.mq = s.f.dev();
+    d.fxy = s.fxy.p;
+    d.fbound = s.fbound.p;
+    d.skipped = s.skipped.p;
     d.cost = s.cost.p;
     d.elen = s.elen.p;
     d.mark = s.mark.p;
@@ -353,6 +358,9 @@ StarArgs star_sub_args(pp_ctx* c, int sub) {
     const size_t r0 = (size_t)q0 * s.f.cap, b0 = (size_t)q0 * kStarKMax;
     StarDev& d = a.sd;
     d.mq = s.f.sub(d.mq, q0, s.f.q_begin(sub + 1));
+    d.fxy += 2 * (size_t)q0;
+    d.fbound += q0;
+    d.skipped += q0;
     d.cost += r0;
     d.elen += r0;
     d.mark += r0;
@@ -553,6 +561,9 @@ int pp_star_new(pp_ctx* ctx, int q, const double* starts, const uint64_t* seeds,
     for (auto* b : {&s.stamp, &s.pn, &s.nnear, &s.bslot, &s.cslot, &s.sA}) PP_HIP(b->reserve(q));
     for (auto* b : {&s.px, &s.py, &s.cb, &s.yA, &s.cA}) PP_HIP(b->reserve(q));
     PP_HIP(s.rew.reserve(q));
+    PP_HIP(s.fxy.reserve(2 * (size_t)q));
+    PP_HIP(s.fbound.reserve(q));
+    PP_HIP(s.skipped.reserve(q));
     for (auto* b : {&s.cmask, &s.bmask}) PP_HIP(b->reserve(q));
     PP_HIP(s.tA.reserve(q));
     for (auto* b : {&s.tB, &s.tC}) PP_HIP(b->reserve(tb));
@@ -569,6 +580,12 @@ int pp_star_new(pp_ctx* ctx, int q, const double* starts, const uint64_t* seeds,
     for (int64_t n = 0; n <= cap64; ++n) ks[n] = star_k(k, (int)n);
     PP_HIP(hipMemcpy(s.ksched.p, ks.data(), ks.size() * sizeof(int), hipMemcpyHostToDevice));
     PP_HIP(hipMemsetAsync(s.mark.p, 0, rows * sizeof(int), st));
+    {  // no focus: every bound +inf, nothing skipped
+        const std::vector<double> inf((size_t)q, std::numeric_limits<double>::infinity());
+        PP_HIP(hipMemcpy(s.fbound.p, inf.data(), q * sizeof(double), hipMemcpyHostToDevice));
+        PP_HIP(hipMemsetAsync(s.fxy.p, 0, 2 * (size_t)q * sizeof(double), st));
+        PP_HIP(hipMemsetAsync(s.skipped.p, 0, q * sizeof(int64_t), st));
+    }
     // (the sub-batch DevStates below are written for the forest's split)
     if ((r = s.f.init(ctx, q, max_iter, step_size, starts, seeds, mq_nsub(q, 3)))) return r;
     // the roots once more (launch_star_init starts with the forest's init kernel), then their
@@ -645,6 +662,46 @@ int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* ya
     const StarBatch& s = ctx->star;
     if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     return s.f.export_tree(ctx, query, x, y, yaw, parent, cap, n, s.cost.p, cost);
+}
+
+static_assert(kStarFocusDraws == PP_STAR_FOCUS_DRAWS && kStarFocusDraws % 64 == 0,
+              "the kernel's draw limit is the header's, in whole wave rounds");
+
+int pp_star_set_focus(pp_ctx* ctx, const double* fxy, const double* bound) {
+    if (!ctx) return set_err(PP_ERR_INVALID_ARGUMENT, "null context");
+    StarBatch& s = ctx->star;
+    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
+    if (!fxy != !bound)
+        return set_err(PP_ERR_INVALID_ARGUMENT, "focus points and bounds: both or neither");
+    const int q = s.f.Q;
+    std::vector<double> inf;
+    if (bound) {
+        for (int i = 0; i < q; ++i)
+            if (!(bound[i] > 0.0))  // (NaN fails the comparison too; +inf: that query has no focus)
+                return set_err(PP_ERR_INVALID_ARGUMENT, "a focus bound must be > 0 or +inf");
+        int r = check_coords(fxy, q, 2, "focus points");
+        if (r || (r = check_coords(fxy + 1, q, 2, "focus points"))) return r;
+    } else {
+        inf.assign((size_t)q, std::numeric_limits<double>::infinity());
+        bound = inf.data();
+    }
+    PP_HIP(hipStreamSynchronize(ctx->stream));
+    if (fxy) PP_HIP(hipMemcpy(s.fxy.p, fxy, 2 * (size_t)q * sizeof(double), hipMemcpyHostToDevice));
+    PP_HIP(hipMemcpy(s.fbound.p, bound, q * sizeof(double), hipMemcpyHostToDevice));
+    return PP_OK;
+}
+
+int pp_star_get_focus(pp_ctx* ctx, double* fxy, double* bound, int64_t* skipped) {
+    if (!ctx) return set_err(PP_ERR_INVALID_ARGUMENT, "null context");
+    const StarBatch& s = ctx->star;
+    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
+    const int q = s.f.Q;
+    hipStream_t st = ctx->stream;
+    if (fxy) PP_HIP(hipMemcpyAsync(fxy, s.fxy.p, 2 * (size_t)q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (bound) PP_HIP(hipMemcpyAsync(bound, s.fbound.p, q * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (skipped) PP_HIP(hipMemcpyAsync(skipped, s.skipped.p, q * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    return PP_OK;
 }
 
 }  // extern "C"

@@ -398,6 +398,9 @@ struct StarBatch {
     DBuf<int> mark, stamp, ksched, pn, near, nnear, bslot, cslot, err;
     DBuf<uint64_t> cmask, bmask;
     DBuf<int64_t> rew;
+    // focused sampling (pp_star_set_focus): focus point [2Q], bound [Q] (+inf none), draws skipped [Q]
+    DBuf<double> fxy, fbound;
+    DBuf<int64_t> skipped;
     DBuf<DevState> state;  // [3 * (1 + kMaxSub)]: rounds A, B, C of the batch, then per sub-batch
     DBuf<SteerTask> tA, tB, tC;
     DBuf<StarTaskExt> eB, eC;

@@ -3878,8 +3878,9 @@ hipError_t launch_mq_steps(hipStream_t s, const MqArgs& a, int steps) {
 // ------------------------------------------------------- RRT* query batch (config 5, §3.7)
 //
 // One lockstep step = one RRT* iteration of every query (oracle/pp_oracle.c orc_star_extend):
-//   star_sample    one wave per query: rand_point, the exact nearest node, Steer(eta) and the
-//                  gate task (new → nearest)                                      → round A
+//   star_sample    one wave per query: rand_point (with a focus: the first draw inside the
+//                  query's ellipse, 64 draws a wave round), the exact nearest node, Steer(eta)
+//                  and the gate task (new → nearest)                              → round A
 //   star_knn       gated queries: X_near = the k nearest nodes of the new point (exact f64,
 //                  (d2, index) order, distances cached in LDS), one choose-parent task per
 //                  X_near node other than the nearest                               → round B
@@ -3941,6 +3942,10 @@ __global__ __launch_bounds__(256) void star_sample_kernel(StarDev sd, double min
     const MqDev& mq = sd.mq;
     for (int q = gw; q < mq.Q; q += nw) {
         const int64_t it = mq.it[q];
+        // (the query's other scalars are read with it: one load latency, not one per use)
+        const uint64_t seed = mq.seed[q];
+        const int64_t skipped = sd.skipped[q];
+        const double L = sd.fbound[q];  // (wave-uniform; +inf: no focus)
         if (it >= mq.target[q]) {
             if (lane == 0) {
                 tasks[q].pnode = -1;
@@ -3948,13 +3953,43 @@ __global__ __launch_bounds__(256) void star_sample_kernel(StarDev sd, double min
             }
             continue;
         }
-        const uint64_t seed = mq.seed[q];
-        double x = gen_range(seed, 2 * (uint64_t)it, minx, maxx);      // rrt.rs:139-146 (Q7)
-        double y = gen_range(seed, 2 * (uint64_t)it + 1, miny, maxy);
-        const int n = mq.n[q];
         const size_t row = (size_t)q * mq.cap;
         const double* __restrict__ X = mq.x + row;
         const double* __restrict__ Y = mq.y + row;
+        // focused sampling (§3.7): the draw counter runs `skipped` ahead of the iteration; with a
+        // finite bound L the sample is the first of the next kStarFocusDraws draws whose distances
+        // to the root and to the focus sum to less than L — 64 draws a round, one per lane
+        uint64_t d = (uint64_t)it + (uint64_t)skipped;
+        if (L < __builtin_inf()) {
+            const double x0 = X[0], y0 = Y[0];
+            const double fx = sd.fxy[2 * (size_t)q], fy = sd.fxy[2 * (size_t)q + 1];
+            int hit = -1;
+            for (int r = 0; r < kStarFocusDraws / 64; ++r) {
+                const uint64_t dl = d + (uint64_t)(64 * r + lane);
+                const double sx = gen_range(seed, 2 * dl, minx, maxx);
+                const double sy = gen_range(seed, 2 * dl + 1, miny, maxy);
+                const double ax = sx - x0, ay = sy - y0, bx = sx - fx, by = sy - fy;
+                const uint64_t in = __ballot(sqrt(ax * ax + ay * ay) + sqrt(bx * bx + by * by) < L);
+                if (in) {  // the lowest draw of the round; every lane redraws it below
+                    hit = 64 * r + (int)__builtin_ctzll(in);
+                    break;
+                }
+            }
+            if (hit < 0) {  // no draw in the set: the iteration ends here (star_knn never sees it)
+                if (lane == 0) {
+                    sd.skipped[q] = (int64_t)(d - (uint64_t)it) + (kStarFocusDraws - 1);
+                    tasks[q].pnode = -1;
+                    sd.pn[q] = -1;
+                    mq.it[q] = it + 1;
+                }
+                continue;
+            }
+            d += (uint64_t)hit;
+            if (lane == 0 && hit > 0) sd.skipped[q] = (int64_t)(d - (uint64_t)it);
+        }
+        double x = gen_range(seed, 2 * d, minx, maxx);      // rrt.rs:139-146 (Q7)
+        double y = gen_range(seed, 2 * d + 1, miny, maxy);
+        const int n = mq.n[q];
         double bd = __builtin_inf();
         int bi = 0x7fffffff;
 #pragma unroll 4

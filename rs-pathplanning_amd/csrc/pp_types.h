@@ -247,8 +247,12 @@ struct MqDev {
 // (X_near), C: the rewire edges X_near → new — each an explicit-task steer_prep / steer_walk pass
 // whose task count the previous kernel sets on the device.
 constexpr int kStarKMax = 63;  // neighbours per insert: with the nearest, <= 64 candidates (lanes)
+constexpr int kStarFocusDraws = 1024;  // PP_STAR_FOCUS_DRAWS: draws an iteration tries (16 wave rounds)
 struct StarDev {
     MqDev mq;            // trees, iteration counters, seeds, blocked roots, targets (K = 1)
+    const double* fxy;   // [2Q] focus point (fx, fy) of the query's sampling set (pp_star_set_focus)
+    const double* fbound;  // [Q] its bound L on |s - root| + |s - focus|; +inf: no focus
+    int64_t* skipped;    // [Q] draws rejected so far: draw index = iteration + skipped
     double* cost;        // [Q * cap] node cost, cost(root) = 0, cost = cost(parent) + elen
     double* elen;        // [Q * cap] Dubins cost of the node's edge to its parent
     int* mark;           // [Q * cap] subtree propagation: level stamp of the node

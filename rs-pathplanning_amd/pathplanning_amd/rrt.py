@@ -745,12 +745,49 @@ class RRTStarBatch:
             return self.revalidate(n_old)
         return self.repair(repair_rounds, n_old)
 
+    # ---- focused sampling (pp_star_set_focus / pp_star_get_focus)
+    def focus(self, goals=None, cost=None):
+        """Informed RRT*: from now on query q samples only where |s - root| + |s - goal| <
+        ``cost[q] * turn_radius`` — the region that can still hold a node of a path cheaper than
+        ``cost[q]`` (``plan``'s unit) — by rejecting draws of its own RNG stream, at most
+        ``PP_STAR_FOCUS_DRAWS`` per iteration.  ``goals``: (q, 2) or (q, 3) rows, or one row for
+        all (a yaw is ignored); a ``cost`` of inf leaves that query unfocused.  ``focus()`` clears
+        every query's focus; the draws skipped so far stay skipped."""
+        if goals is None and cost is None:
+            _ffi.check(_ffi.lib().pp_star_set_focus(self.ctx.handle, None, None))
+            return
+        if goals is None or cost is None:
+            raise ValueError("focus() takes both goals and cost, or neither")
+        g = np.asarray(goals, dtype=np.float64)
+        g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
+        fxy = np.ascontiguousarray(g.reshape(self.q, -1)[:, :2])
+        cost = np.broadcast_to(np.asarray(cost, dtype=np.float64), (self.q,))
+        bound = np.ascontiguousarray(cost * np.float64(self.space.get_steer()))
+        dp = C.POINTER(C.c_double)
+        _ffi.check(_ffi.lib().pp_star_set_focus(self.ctx.handle, fxy.ctypes.data_as(dp),
+                                                bound.ctypes.data_as(dp)))
+
+    def focus_state(self):
+        """(fxy float64[q, 2], bound float64[q] in length units (inf: no focus), skipped int64[q]:
+        the draws each query's filter has rejected so far)"""
+        fxy, bound = np.zeros((self.q, 2)), np.zeros(self.q)
+        skipped = np.zeros(self.q, dtype=np.int64)
+        dp = C.POINTER(C.c_double)
+        _ffi.check(_ffi.lib().pp_star_get_focus(
+            self.ctx.handle, fxy.ctypes.data_as(dp), bound.ctypes.data_as(dp),
+            skipped.ctypes.data_as(C.POINTER(C.c_int64))))
+        return fxy, bound, skipped
+
     # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path, DESIGN.md §3.7)
-    def plan(self, goals):
+    def plan(self, goals, focus: bool = False):
         """The cheapest feasible goal edge of every query on its tree as extended so far: goal
         (gx, gy, gyaw) per query (one pose is broadcast to all).  Returns (best_node int32[q],
         cost float64[q]): -1 and inf where no node reaches the goal.  ``n_checked``: the
-        (query, node) pairs considered."""
+        (query, node) pairs considered.  ``focus``: then ``focus(goals, cost)`` on the result."""
+        if focus:
+            node, cost = self.plan(goals)
+            self.focus(goals, cost)
+            return node, cost
         g = np.asarray(goals, dtype=np.float64)
         g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
         g = np.ascontiguousarray(g, dtype=np.float64).reshape(self.q, 3)
