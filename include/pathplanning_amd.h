@@ -44,7 +44,8 @@ extern "C" {
  * 5 (+): PP_COORD_MAX, pp_coord_check and pp_sincos_small_batch added; positions above
  *    PP_COORD_MAX are now PP_ERR_INVALID_ARGUMENT, nothing else changed
  * 5 (+): PP_STAR_FOCUS_DRAWS, pp_star_set_focus and pp_star_get_focus added (focused sampling of
- *    the RRT* batch); a batch that never sets a focus runs as before bit for bit */
+ *    the RRT* batch); a batch that never sets a focus runs as before bit for bit
+ * 5 (+): pp_star_prune added, nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -439,8 +440,8 @@ int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* ya
  * Either way it += 1: a step is still one iteration per query, and max_iter, the tree capacity
  * and the k schedule are untouched; only the draw counter runs ahead.  An empty set (L at most the
  * distance between the root and the focus) is legal: every iteration then rejects all its draws.
- * pp_star_revalidate, pp_star_repair, pp_space_*, pp_star_plan and pp_star_paths leave the focus
- * and skipped alone; only pp_star_set_focus and pp_star_new change them. */
+ * pp_star_revalidate, pp_star_repair, pp_star_prune, pp_space_*, pp_star_plan and pp_star_paths
+ * leave the focus and skipped alone; only pp_star_set_focus and pp_star_new change them. */
 #define PP_STAR_FOCUS_DRAWS 1024
 /* fxy: q rows (fx, fy); bound: q values L.  Both NULL: every query's focus is cleared (L = +inf),
  * skipped is kept.  PP_ERR_INVALID_ARGUMENT for exactly one NULL, for a bound that is NaN, <= 0 or
@@ -449,6 +450,39 @@ int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* ya
 int pp_star_set_focus(pp_ctx* ctx, const double* fxy, const double* bound);
 /* fxy (2q), bound (q), skipped (q int64); each may be NULL */
 int pp_star_get_focus(pp_ctx* ctx, double* fxy, double* bound, int64_t* skipped);
+/* Pruning by the focus bound (build-defined, DESIGN.md §3.7 "Pruning by the focus bound"; CPU
+ * restatement tests/star_prune_ref.py): the second half of Informed RRT*.  One call prunes every
+ * query's tree against the query's stored focus, the (fx, fy), L that pp_star_set_focus set and
+ * pp_star_get_focus reads back.  R is the turn radius of the context's current Space.
+ *   Node test.  Node i > 0 of query q fails iff
+ *       cost[i] * R + sqrt((x[i]-fx)*(x[i]-fx) + (y[i]-fy)*(y[i]-fy)) > L
+ *     in f64, uncontracted (every product and sum rounded on its own), the square root correctly
+ *     rounded; cost is the stored cost-to-come in pp_star_tree_export's unit.  The comparison is
+ *     strict: a node exactly on the bound stays.  The heuristic is admissible (a Dubins path is
+ *     never shorter than the distance between its ends): a failing node cannot lie, at its current
+ *     cost, on a path to the focus of length <= L.  With L = +inf the test never fails.
+ *   Protected chain.  keep[q] is a node of query q's tree, or -1.  Every node on the chain
+ *     keep[q] -> parent -> ... -> root passes, whatever the node test says: with L = (pp_star_plan's
+ *     cost) * R and a straight goal edge the best node sits exactly on the bound, and one ulp of
+ *     rounding in cost * R would otherwise drop the path that defined the bound.  keep =
+ *     pp_star_plan's best_node is the intended use; keep NULL means all -1.
+ *   Keep rule (pp_star_revalidate's).  The root always stays.  Node i stays iff it and every node
+ *     on its chain to the root pass, so a failing node takes its descendants with it; chains are
+ *     not index-ordered (a rewired node's parent may be a later node), and a chain that does not
+ *     end in its tree's root is dropped.
+ *   Compaction (pp_star_revalidate's).  Kept nodes keep their order and their x, y, yaw, cost and
+ *     edge cost bit for bit; parents are remapped and may still exceed their child's index.
+ * Untouched: the focus and skipped; the iteration counters, seeds, k, eta, step size and max_iter;
+ * the per-query evaluations and rewires and pp_stats; the blocked roots of polygon mode.  The
+ * scene is not consulted beyond R: the call neither verifies nor un-verifies anything.  Caveat: a
+ * pruned node could have been made cheaper by a later rewire and then have passed — the usual
+ * branch-and-bound trade of Informed RRT* (DESIGN.md §3.7 measures what it costs).
+ * keep: q entries, or NULL.  n_nodes, n_dropped, new_index: exactly pp_star_revalidate's, each may
+ * be NULL; new_index is laid out at the prefix sums of the sizes before the call.  PP_ERR_STATE
+ * without an RRT* batch or a scene.  PP_ERR_INVALID_ARGUMENT for a keep[q] outside [-1, n_q),
+ * checked on the host before anything is launched: trees and focus are unchanged. */
+int pp_star_prune(pp_ctx* ctx, const int32_t* keep, int32_t* n_nodes, int64_t* n_dropped,
+                  int32_t* new_index);
 /* Re-verify every query's tree of the RRT* batch against the context's current Space and drop
  * what no longer holds (build-defined; CPU restatement
  * tests/star_revalidate_ref.py).  The edge of node i > 0 is RRT*'s feasible edge (§3.7) from its

@@ -10,6 +10,7 @@
 //   pp_revalidate.cpp  a tree across a scene change: pp_rrt_revalidate, pp_batch_revalidate,
 //                      pp_star_revalidate
 //   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
+//   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -434,6 +435,8 @@ struct Reval {
     DBuf<int> lvl, wpar, tops, tslot, tcnt, near;
     DBuf<double> wcost, welen, tcost;
     DBuf<RepairRec> rrec;
+    // pp_star_prune only (PruneArgs)
+    DBuf<int> keep;
 };
 
 // ---- profiling
@@ -524,7 +527,8 @@ int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines
                 double* len_host = nullptr);
 // The two host halves of a revalidation around its launches (pp_revalidate.cpp), shared with
 // pp_star_repair (pp_repair.cpp).  reval_setup: the buffers (the steer slice's for at least
-// min_tasks tasks), the offsets and blocked roots on the device, the kernel arguments and the
+// min_tasks tasks; min_tasks < 0: no steer slice and no literal pool, pp_star_prune's verdicts
+// need neither), the offsets and blocked roots on the device, the kernel arguments and the
 // doubling passes, for Q trees of hn[q] nodes in the rows tr (tree q at q * cap).  reval_finish:
 // the kept nodes over all trees, new_index (may be null) and the error word after one
 // synchronisation; PP_ERR_STEER_OVERFLOW when a steer overflowed (the trees are unmodified).

@@ -387,6 +387,19 @@ hipError_t launch_repair_knn(hipStream_t s, const RepairArgs& a, int ntops);
 hipError_t launch_repair_slice(hipStream_t s, const SceneDev& sc, const RepairArgs& a, int t0,
                                int t1);
 
+// Prune (pp_star_prune, pp_k_prune.hip; DESIGN.md §3.7 "Pruning by the focus bound"): the keep
+// words of an RRT* forest by its queries' focus bounds, in front of launch_reval_jump and
+// launch_reval_compact.  No steer: rv's slice buffers are unused.
+struct PruneArgs {
+    RevalArgs rv;                    // the forest (any_order, cost), its offsets, v[0]
+    const double* fxy = nullptr;     // [2Q] the queries' focus points (StarArgs::fxy, whole batch)
+    const double* fbound = nullptr;  // [Q] their bounds L, +inf: no focus
+    double R = 0.0;                  // the scene's turn radius: cost * R is a length
+    const int* keep = nullptr;       // [Q] the protected chain's first node, -1 none (null: none)
+};
+// the node test of every node into rv.v[0], then the protected chains
+hipError_t launch_prune_verdicts(hipStream_t s, const PruneArgs& p);
+
 // dubins_path_planning_from_origin for n (dx, dy, eyaw, c, step_size) configurations
 hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int cap, double* px,
                                 double* py, double* pyaw, int* n_out, int* word_out,

@@ -27,7 +27,8 @@ int reval_setup(pp_ctx* c, const TreeDev& tr, int Q, size_t cap, const std::vect
     const int total = (int)total64;
     const size_t z = (size_t)total;
     const int slice = std::min(total, kRevalSlice);
-    const int tasks = std::max(slice, min_tasks);
+    const bool steers = min_tasks >= 0;  // (pp_star_prune: verdicts without a steer round)
+    const int tasks = steers ? std::max(slice, min_tasks) : 0;
     PP_HIP(r.tasks.reserve(tasks));
     PP_HIP(r.ext.reserve(tasks));
     PP_HIP(r.rec.reserve(tasks));
@@ -48,7 +49,7 @@ int reval_setup(pp_ctx* c, const TreeDev& tr, int Q, size_t cap, const std::vect
     if (blocked) PP_HIP(r.blocked.reserve(Q));
     hipStream_t st = c->stream;
     int rc;
-    if ((rc = ensure_literal_pool(c, st))) return rc;
+    if (steers && (rc = ensure_literal_pool(c, st))) return rc;
     PP_HIP(hipMemcpy(r.off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
     if (blocked) PP_HIP(hipMemcpy(r.blocked.p, blocked, Q, hipMemcpyHostToDevice));
     PP_HIP(hipMemsetAsync(r.state.p, 0, sizeof(DevState), st));

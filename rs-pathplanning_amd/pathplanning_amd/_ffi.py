@@ -48,7 +48,7 @@ EXPORTED = [
     "pp_batch_plan", "pp_batch_paths",
     "pp_rrt_revalidate", "pp_batch_revalidate",
     "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export", "pp_star_revalidate",
-    "pp_star_repair", "pp_star_set_focus", "pp_star_get_focus",
+    "pp_star_repair", "pp_star_set_focus", "pp_star_get_focus", "pp_star_prune",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
     "pp_coord_check", "pp_sincos_small_batch",
@@ -183,6 +183,7 @@ def lib():
             "pp_star_repair": ([vp, C.c_int, ip, i64p, i64p, i64p, ip], C.c_int),
             "pp_star_set_focus": ([vp, dp, dp], C.c_int),
             "pp_star_get_focus": ([vp, dp, dp, i64p], C.c_int),
+            "pp_star_prune": ([vp, ip, ip, i64p, ip], C.c_int),
             "pp_star_state": ([vp, ip, i64p, i64p, i64p], C.c_int),
             "pp_star_tree_export": ([vp, C.c_int, dp, dp, dp, ip, dp, C.c_int64, i64p], C.c_int),
             "pp_star_plan": ([vp, dp, ip, dp, i64p], C.c_int),

@@ -778,15 +778,50 @@ class RRTStarBatch:
             skipped.ctypes.data_as(C.POINTER(C.c_int64))))
         return fxy, bound, skipped
 
+    def prune(self, keep=None, n_old=None):
+        """Informed RRT*'s other half (pp_star_prune): drop from every query's tree the nodes
+        that, at their stored cost, cannot lie on a path to the query's focus within its bound —
+        node i > 0 fails iff ``cost[i] * turn_radius + |node - focus| > bound`` (``focus_state``'s
+        values; strict) — and their descendants.  ``keep``: one node per query (-1: none), e.g.
+        ``plan``'s best nodes: the chain from it to the root stays whatever the test says.  An
+        unfocused query keeps every node.  Kept nodes keep their order, pose and cost; parents
+        are remapped; the focus, counters and seeds stay.  Returns (n_nodes, new_index) as
+        ``revalidate`` does and sets ``last_dropped``.  A node pruned now could have been made
+        cheaper by a later rewire: the usual branch-and-bound trade."""
+        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
+        total = int(n_old.sum(dtype=np.int64))
+        new_index = np.zeros(max(total, 1), dtype=np.int32)
+        n = np.zeros(self.q, dtype=np.int32)
+        dropped = C.c_int64(0)
+        ip = C.POINTER(C.c_int32)
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.int32).reshape(self.q)
+        _ffi.check(_ffi.lib().pp_star_prune(
+            self.ctx.handle, None if keep is None else keep.ctypes.data_as(ip),
+            n.ctypes.data_as(ip), C.byref(dropped), new_index.ctypes.data_as(ip)))
+        self.last_dropped = dropped.value
+        return n, new_index[:total]
+
     # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path, DESIGN.md §3.7)
-    def plan(self, goals, focus: bool = False):
+    def plan(self, goals, focus: bool = False, prune: bool = False):
         """The cheapest feasible goal edge of every query on its tree as extended so far: goal
         (gx, gy, gyaw) per query (one pose is broadcast to all).  Returns (best_node int32[q],
         cost float64[q]): -1 and inf where no node reaches the goal.  ``n_checked``: the
-        (query, node) pairs considered.  ``focus``: then ``focus(goals, cost)`` on the result."""
+        (query, node) pairs considered.  ``focus``: then ``focus(goals, cost)`` on the result.
+        ``prune`` (needs ``focus``): then ``prune(keep=best_node)``; the best nodes returned are
+        their indices in the pruned trees."""
+        if prune and not focus:
+            raise ValueError("plan(prune=True) needs focus=True: the prune reads the focus")
         if focus:
             node, cost = self.plan(goals)
             self.focus(goals, cost)
+            if prune:
+                n_old = self.state()[0]
+                _, new_index = self.prune(keep=node, n_old=n_old)
+                off = np.concatenate(([0], np.cumsum(n_old[:-1], dtype=np.int64)))
+                has = node >= 0
+                node = node.copy()
+                node[has] = new_index[off[has] + node[has]]
             return node, cost
         g = np.asarray(goals, dtype=np.float64)
         g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
