@@ -45,7 +45,10 @@ extern "C" {
  *    PP_COORD_MAX are now PP_ERR_INVALID_ARGUMENT, nothing else changed
  * 5 (+): PP_STAR_FOCUS_DRAWS, pp_star_set_focus and pp_star_get_focus added (focused sampling of
  *    the RRT* batch); a batch that never sets a focus runs as before bit for bit
- * 5 (+): pp_star_prune added, nothing else changed */
+ * 5 (+): pp_star_prune added, nothing else changed
+ * 5 (+): pp_forest_state, pp_star_forest_export / pp_star_forest_import and
+ *        pp_batch_forest_export / pp_batch_forest_import added (the complete state of a set of
+ *        query slots out of a batch and into one), nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -566,6 +569,92 @@ int pp_star_path(pp_ctx* ctx, int query, const double goal[3], int32_t node, dou
  * outside its query's tree.  The trees are not modified. */
 int pp_star_paths(pp_ctx* ctx, const double* goals, const int32_t* nodes, int64_t* off, double* x,
                   double* y, int64_t cap, int64_t* n_total, double* length, uint8_t* ok);
+
+/* ------------------------------------- forest export / import (build-defined) */
+/* The complete state of m query slots of a batch, packed: what a checkpoint, a move of a query to
+ * another context or the recycling of a finished query's slot needs (CPU restatement of the
+ * validation and the cost rebuild: tests/forest_state_ref.py).  A plain struct of caller-owned
+ * arrays; `size` = sizeof(pp_forest_state) as the caller compiled it (fields past it read as
+ * NULL).  Rows are CSR over the m served slots: slot i's tree is rows [off[i], off[i + 1]), root
+ * first, in the tree's own node order.
+ *   rows:      off (m + 1), x, y, yaw (f64), parent (int32, -1 for a tree's row 0),
+ *              cost, edge_cost (f64; RRT* only, cost in pp_star_tree_export's unit)
+ *   per slot:  iterations, seeds, node_evals (m each); RRT*: rewires, focus_xy (2m), focus_bound
+ *              (m, +inf: no focus), skipped; the extend batch: goals (3m)
+ * Arrays of the other batch kind are ignored by both directions. */
+typedef struct pp_forest_state {
+    uint64_t size;
+    int64_t* off;
+    double* x;
+    double* y;
+    double* yaw;
+    int32_t* parent;
+    double* cost;
+    double* edge_cost;
+    int64_t* iterations;
+    uint64_t* seeds;
+    int64_t* node_evals;
+    int64_t* rewires;
+    double* focus_xy;
+    double* focus_bound;
+    int64_t* skipped;
+    double* goals;
+} pp_forest_state;
+/* Export the slots queries[0 .. m) (m distinct slots in any order; NULL: the slots 0 .. m - 1) of
+ * the RRT* batch into *state.  Any pointer of *state may be NULL: that part is skipped.  Sizing as
+ * pp_star_paths: with every row pointer (x, y, yaw, parent, cost, edge_cost) NULL or cap <= 0 the
+ * call returns the sizes only — off, the per-slot arrays and *n_total = off[m] are filled, PP_OK;
+ * cap < *n_total (cap: the rows each row array holds) is PP_ERR_CAPACITY with the same outputs
+ * filled.  The rows are gathered and packed on the device into one staging buffer per array and
+ * copied out once per array (into pageable memory); there is no per-query copy or synchronisation.
+ * Nothing in the batch is modified.  PP_ERR_STATE without an RRT* batch; PP_ERR_INVALID_ARGUMENT
+ * for a NULL state or n_total, a state->size that does not reach `off`, m outside [1, q], a slot
+ * out of range or named twice. */
+int pp_star_forest_export(pp_ctx* ctx, const int32_t* queries, int m, pp_forest_state* state,
+                          int64_t cap, int64_t* n_total);
+/* Write *state into the slots queries[0 .. m) of the RRT* batch; every other slot stays untouched
+ * bit for bit.  Everything is validated before any row of the forest is written: a failed call
+ * leaves the batch unchanged bit for bit and sets *bad_query (may be NULL) to the first offending
+ * entry of `queries` (the slot number; with queries NULL, the index).
+ *   On the host, before anything is launched: every pointer but `cost` present; distinct slots in
+ *   range; off[0] = 0 and n_i = off[i + 1] - off[i] >= 1; iterations within [0, max_iter];
+ *   n_i <= iterations_i + 1, else PP_ERR_CAPACITY (a tree has max_iter + 1 rows and may still
+ *   insert max_iter - iterations nodes; a tree pruned below that is fine); node_evals, rewires and
+ *   skipped >= 0; pp_coord_check of the positions; finite yaw; finite edge_cost >= 0;
+ *   pp_star_set_focus' rules for the bound and the focus row; in polygon mode a tree of more than
+ *   one node on a root that fails verify is refused (this library never grows one).
+ *   On the device, one pass over the staged rows, one wave per tree: row 0 has parent -1; every
+ *   other parent lies in [0, n_i) and is not the node itself; every chain ends in row 0 (no cycle,
+ *   no island — decided level by level from the root, without assuming index order: a rewired
+ *   node's parent may be a later node); cost[0] = 0 and cost[i] = cost[parent[i]] + edge_cost[i],
+ *   rebuilt parents before children as one f64 addition each, uncontracted.  A `cost` the caller
+ *   passed must equal the rebuilt values bit for bit (a damaged checkpoint fails here); with cost
+ *   NULL the rebuilt values are stored.
+ * All of these are PP_ERR_INVALID_ARGUMENT except the capacity.  Then the rows, counters, seeds,
+ * focus state and the stored root (row 0's pose) are scattered into the slots, and what the
+ * library derives for a slot is derived again: the polygon-mode blocked flag of the new root and
+ * RRT*'s rewire scratch.  The outcome does not depend on what the slot held before.
+ * Import trusts the edges, as pp_rrt_tree_import does: it neither steers nor verifies.  A tree
+ * that comes from another scene: import, then pp_star_revalidate.
+ * Unchanged: k, eta, step size, max_iter, pp_stats, the other slots, the scene.
+ *
+ * The guarantee.  Batch A of some size and batch B of any size, on the same scene, step size,
+ * max_iter, k and eta: export any slots of A at any step and import them into any slots of B.
+ * Under further extend / plan / focus / prune calls those slots of B evolve exactly as the slots of
+ * A do: x, y, yaw, parent, cost, edge cost, iterations, skipped, evaluations and rewires are equal
+ * bit for bit.  The queries are independent and the state is complete. */
+int pp_star_forest_import(pp_ctx* ctx, const int32_t* queries, int m,
+                          const pp_forest_state* state, int32_t* bad_query);
+/* The same pair for the extend batch (pp_batch_new): rows x, y, yaw, parent; per slot iterations,
+ * seeds, node_evals and goals.  Export accepts a batch that a scene change invalidated (stale);
+ * import needs a valid one.  Import requires parent[i] < i for every row i > 0 (pp_rrt_tree_import's
+ * rule; the extend never rewires), finite goals, and voids the slot's verdict cache.  The guarantee
+ * above holds with the window in place of k and eta (the trees do not depend on it).  A tree from
+ * another scene: import, then pp_batch_revalidate. */
+int pp_batch_forest_export(pp_ctx* ctx, const int32_t* queries, int m, pp_forest_state* state,
+                           int64_t cap, int64_t* n_total);
+int pp_batch_forest_import(pp_ctx* ctx, const int32_t* queries, int m,
+                           const pp_forest_state* state, int32_t* bad_query);
 
 int pp_rrt_get_stats(pp_ctx* ctx, pp_stats* out, uint64_t out_size);
 int pp_rrt_reset_stats(pp_ctx* ctx);

@@ -11,6 +11,7 @@
 //                      pp_star_revalidate
 //   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
 //   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
+//   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -439,6 +440,17 @@ struct Reval {
     DBuf<int> keep;
 };
 
+// ---- packed forest export / import (pp_*_forest_export / pp_*_forest_import: ForestIoArgs), sized
+// to the call: the served slots, their row offsets, one staging buffer per row array and per
+// per-slot array, the validation's levels and verdicts
+struct ForestIo {
+    DBuf<int> slots, spar, lvl, verdict;
+    DBuf<int64_t> off, sit, sevals, srew, sskipped;
+    DBuf<uint64_t> sseed;
+    DBuf<double> sx, sy, syaw, scost, selen, scost_in, sfxy, sfbound;
+    DBuf<uint8_t> sblocked;
+};
+
 // ---- profiling
 struct Profiling {
     bool on = false;
@@ -486,6 +498,7 @@ struct pp_ctx {
     ppamd::StarBatch star;
     ppamd::PathExport paths;
     ppamd::Reval reval;
+    ppamd::ForestIo fio;
     ppamd::Profiling prof;
 
     // the scene as the one-tree planner's kernels see it (its step, its blocked root)

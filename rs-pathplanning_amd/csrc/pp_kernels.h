@@ -400,6 +400,66 @@ struct PruneArgs {
 // the node test of every node into rv.v[0], then the protected chains
 hipError_t launch_prune_verdicts(hipStream_t s, const PruneArgs& p);
 
+// Forest export / import (pp_*_forest_export / pp_*_forest_import, pp_k_forest_io.hip; DESIGN.md
+// §3.9): the complete state of the slots slots[0 .. m) of a forest, packed.  Staged row k of the
+// packed arrays belongs to served slot i with off[i] <= k < off[i + 1] and is row slots[i] * cap +
+// (k - off[i]) of the forest.  Null forest pointers: that array does not exist in this batch kind
+// (cost .. stamp: RRT*; itprev: the extend batch) or is not wanted.
+struct ForestIoArgs {
+    TreeDev tr{};
+    size_t cap = 0;
+    int m = 0;
+    const int* slots = nullptr;   // [m] distinct slots of the forest
+    int64_t* off = nullptr;       // [m + 1] exclusive scan of the served trees' node counts
+    int64_t total = 0;            // off[m] (the row kernels' bound)
+    // the forest: per row ...
+    double* cost = nullptr;
+    double* elen = nullptr;
+    int* mark = nullptr;
+    // ... and per slot
+    int* n = nullptr;
+    int64_t* it = nullptr;
+    int64_t* evals = nullptr;
+    uint64_t* seed = nullptr;
+    int64_t* rew = nullptr;
+    double* fxy = nullptr;
+    double* fbound = nullptr;
+    int64_t* skipped = nullptr;
+    int* stamp = nullptr;
+    double* starts = nullptr;     // [3Q] the stored roots (Forest::d_starts)
+    uint8_t* blocked = nullptr;   // [Q] or null: no blocked roots in this forest
+    int64_t* itprev = nullptr;
+    // the staged rows [total] ...
+    double* sx = nullptr;
+    double* sy = nullptr;
+    double* syaw = nullptr;
+    int* spar = nullptr;
+    double* scost = nullptr;            // export: the costs; import: the rebuilt costs
+    double* selen = nullptr;
+    const double* scost_in = nullptr;   // import: the caller's costs to check against (or null)
+    int* lvl = nullptr;                 // import: the validation's levels (0: not reached)
+    // ... and the staged per-slot values [m]
+    int64_t* sit = nullptr;
+    int64_t* sevals = nullptr;
+    uint64_t* sseed = nullptr;
+    int64_t* srew = nullptr;
+    double* sfxy = nullptr;
+    double* sfbound = nullptr;
+    int64_t* sskipped = nullptr;
+    const uint8_t* sblocked = nullptr;  // import: the new roots' blocked flags
+    int ordered = 0;                    // import: parent[i] < i required (the extend batch)
+    int* verdict = nullptr;             // [m] import: 0 or the first rule the tree breaks (kFio*)
+};
+enum : int { kFioOk = 0, kFioRoot = 1, kFioParent = 2, kFioOrder = 3, kFioUnreached = 4, kFioCost = 5 };
+// off[0 .. m] from the served slots' node counts, and their per-slot values into the staged ones
+hipError_t launch_forest_sizes(hipStream_t s, const ForestIoArgs& a);
+// the served trees' rows into the staged arrays (a null staged array is skipped)
+hipError_t launch_forest_gather(hipStream_t s, const ForestIoArgs& a);
+// verdict[i] of every staged tree and, for RRT*, the rebuilt costs in scost; one wave per tree
+hipError_t launch_forest_validate(hipStream_t s, const ForestIoArgs& a);
+// the staged rows and per-slot values into the forest, and the slots' derived state
+hipError_t launch_forest_scatter(hipStream_t s, const ForestIoArgs& a);
+
 // dubins_path_planning_from_origin for n (dx, dy, eyaw, c, step_size) configurations
 hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int cap, double* px,
                                 double* py, double* pyaw, int* n_out, int* word_out,

@@ -50,6 +50,8 @@ EXPORTED = [
     "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export", "pp_star_revalidate",
     "pp_star_repair", "pp_star_set_focus", "pp_star_get_focus", "pp_star_prune",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
+    "pp_star_forest_export", "pp_star_forest_import", "pp_batch_forest_export",
+    "pp_batch_forest_import",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
     "pp_coord_check", "pp_sincos_small_batch",
 ]
@@ -86,6 +88,32 @@ class StatsC(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_abi3"}
+
+
+class ForestStateC(C.Structure):
+    """pp_forest_state: caller-owned arrays, ``size`` first."""
+    _fields_ = [
+        ("size", C.c_uint64), ("off", C.POINTER(C.c_int64)),
+        ("x", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)),
+        ("yaw", C.POINTER(C.c_double)), ("parent", C.POINTER(C.c_int32)),
+        ("cost", C.POINTER(C.c_double)), ("edge_cost", C.POINTER(C.c_double)),
+        ("iterations", C.POINTER(C.c_int64)), ("seeds", C.POINTER(C.c_uint64)),
+        ("node_evals", C.POINTER(C.c_int64)), ("rewires", C.POINTER(C.c_int64)),
+        ("focus_xy", C.POINTER(C.c_double)), ("focus_bound", C.POINTER(C.c_double)),
+        ("skipped", C.POINTER(C.c_int64)), ("goals", C.POINTER(C.c_double)),
+    ]
+
+
+# the arrays of a forest state dict (RRTStarBatch / RRTBatch export_forest): dtype, entries per
+# slot (0: per row), the batch kinds that carry it
+FOREST_FIELDS = {
+    "off": ("int64", 1, "sb"), "x": ("float64", 0, "sb"), "y": ("float64", 0, "sb"),
+    "yaw": ("float64", 0, "sb"), "parent": ("int32", 0, "sb"), "cost": ("float64", 0, "s"),
+    "edge_cost": ("float64", 0, "s"), "iterations": ("int64", 1, "sb"),
+    "seeds": ("uint64", 1, "sb"), "node_evals": ("int64", 1, "sb"), "rewires": ("int64", 1, "s"),
+    "focus_xy": ("float64", 2, "s"), "focus_bound": ("float64", 1, "s"),
+    "skipped": ("int64", 1, "s"), "goals": ("float64", 3, "b"),
+}
 
 
 _lock = threading.Lock()
@@ -191,6 +219,12 @@ def lib():
             "pp_star_path": ([vp, C.c_int, dp, C.c_int32, dp, dp, C.c_int64, i64p, dp], C.c_int),
             "pp_star_paths": ([vp, dp, ip, i64p, dp, dp, C.c_int64, i64p, dp,
                                C.POINTER(C.c_uint8)], C.c_int),
+            "pp_star_forest_export": ([vp, ip, C.c_int, C.POINTER(ForestStateC), C.c_int64, i64p],
+                                      C.c_int),
+            "pp_star_forest_import": ([vp, ip, C.c_int, C.POINTER(ForestStateC), ip], C.c_int),
+            "pp_batch_forest_export": ([vp, ip, C.c_int, C.POINTER(ForestStateC), C.c_int64, i64p],
+                                       C.c_int),
+            "pp_batch_forest_import": ([vp, ip, C.c_int, C.POINTER(ForestStateC), ip], C.c_int),
             "pp_rrt_get_stats": ([vp, C.POINTER(StatsC), C.c_uint64], C.c_int),
             "pp_rrt_reset_stats": ([vp], C.c_int),
             "pp_set_profiling": ([vp, C.c_int], C.c_int),

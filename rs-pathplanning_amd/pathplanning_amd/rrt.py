@@ -476,6 +476,97 @@ class RRT:  # rrt.rs:325-620
         self.ctx.close()
 
 
+def _forest_slots(queries, q):
+    """(slot array or None, its ctypes pointer or None, m) of an export / import call"""
+    if queries is None:
+        return None, None, q
+    s = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+    return s, s.ctypes.data_as(C.POINTER(C.c_int32)), len(s)
+
+
+def _forest_struct(kind, arrays):
+    """pp_forest_state over the dict's arrays of this batch kind ('s' RRT*, 'b' extend)"""
+    st = _ffi.ForestStateC()
+    st.size = C.sizeof(st)
+    for name, (_, _, kinds) in _ffi.FOREST_FIELDS.items():
+        a = arrays.get(name)
+        if a is not None and kind in kinds:
+            setattr(st, name, a.ctypes.data_as(type(getattr(st, name))))
+    return st
+
+
+def _forest_export(ctx, kind, q, queries):
+    """pp_star_forest_export / pp_batch_forest_export: the sizes, then the rows.  A dict of numpy
+    arrays (``_ffi.FOREST_FIELDS``), usable with ``np.savez`` / ``np.load`` as it is."""
+    L = _ffi.lib()
+    fn = L.pp_star_forest_export if kind == "s" else L.pp_batch_forest_export
+    _, sp, m = _forest_slots(queries, q)
+    out = {name: np.zeros(m * per + (name == "off"), dtype=dt)
+           for name, (dt, per, kinds) in _ffi.FOREST_FIELDS.items() if per and kind in kinds}
+    tot = C.c_int64(0)
+    st = _forest_struct(kind, out)
+    _ffi.check(fn(ctx.handle, sp, m, C.byref(st), 0, C.byref(tot)))
+    n = tot.value
+    for name, (dt, per, kinds) in _ffi.FOREST_FIELDS.items():
+        if not per and kind in kinds:
+            out[name] = np.zeros(n, dtype=dt)
+    st = _forest_struct(kind, out)
+    _ffi.check(fn(ctx.handle, sp, m, C.byref(st), n, C.byref(tot)))
+    if "focus_xy" in out:
+        out["focus_xy"] = out["focus_xy"].reshape(m, 2)
+    if "goals" in out:
+        out["goals"] = out["goals"].reshape(m, 3)
+    return out
+
+
+def _forest_import(ctx, kind, state, queries):
+    """pp_star_forest_import / pp_batch_forest_import of a state dict (a missing or None entry is
+    passed as NULL: only ``cost`` may be).  A refused call raises PPError with ``bad_query`` = the
+    first offending slot (-1: none named) and leaves the batch as it was."""
+    L = _ffi.lib()
+    fn = L.pp_star_forest_import if kind == "s" else L.pp_batch_forest_import
+    arrays = {}
+    if state is not None:
+        for name, (dt, _, kinds) in _ffi.FOREST_FIELDS.items():
+            if kind in kinds and state.get(name) is not None:
+                arrays[name] = np.ascontiguousarray(state[name], dtype=dt).reshape(-1)
+    m = len(arrays["off"]) - 1 if "off" in arrays else 0
+    _, sp, mq = _forest_slots(queries, m)
+    if queries is not None and mq != m and state is not None:
+        raise ValueError(f"{mq} query slots for a state of {m} trees")
+    for name, (_, per, kinds) in _ffi.FOREST_FIELDS.items():
+        if name in arrays and name != "off":
+            want = m * per if per else int(arrays["off"][-1]) if m > 0 else 0
+            if len(arrays[name]) < want:
+                raise ValueError(f"state[{name!r}] holds {len(arrays[name])} entries, {want} needed")
+    bad = C.c_int32(-1)
+    st = _forest_struct(kind, arrays)
+    try:
+        _ffi.check(fn(ctx.handle, sp, mq, C.byref(st) if state is not None else None,
+                      C.byref(bad)))
+    except _ffi.PPError as e:
+        e.bad_query = bad.value
+        raise
+
+
+def _forest_roots(kind, starts, seeds, goals=None):
+    """the state of root-only trees: what pp_star_new / pp_batch_new leave in a slot"""
+    starts = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+    m = len(starts)
+    st = {"off": np.arange(m + 1, dtype=np.int64), "x": starts[:, 0].copy(),
+          "y": starts[:, 1].copy(), "yaw": starts[:, 2].copy(),
+          "parent": np.full(m, -1, dtype=np.int32), "iterations": np.zeros(m, dtype=np.int64),
+          "seeds": np.ascontiguousarray(seeds, dtype=np.uint64).reshape(m),
+          "node_evals": np.zeros(m, dtype=np.int64)}
+    if kind == "s":
+        st.update(cost=np.zeros(m), edge_cost=np.zeros(m), rewires=np.zeros(m, dtype=np.int64),
+                  focus_xy=np.zeros((m, 2)), focus_bound=np.full(m, np.inf),
+                  skipped=np.zeros(m, dtype=np.int64))
+    else:
+        st["goals"] = np.ascontiguousarray(goals, dtype=np.float64).reshape(m, 3)
+    return st
+
+
 class RRTBatch:
     """Many independent planners on one scene (BASELINE config 3): ``RRT::new`` per query
     (rrt.rs:335-355) with its own start, goal and sampling stream, advanced in lockstep — one
@@ -622,6 +713,28 @@ class RRTBatch:
             self.ctx.handle, int(query), x.ctypes.data_as(dp), y.ctypes.data_as(dp),
             yaw.ctypes.data_as(dp), par.ctypes.data_as(ip), n, C.byref(out)))
         return x, y, yaw, par
+
+    # ---- forest export / import (pp_batch_forest_export / _import)
+    def export_forest(self, queries=None):
+        """The complete state of the slots ``queries`` (distinct, any order; None: all) in one
+        call, packed: a dict of numpy arrays — ``off`` int64[m + 1] (slot i's tree is rows
+        off[i]:off[i + 1]), rows ``x``, ``y``, ``yaw``, ``parent``, per slot ``iterations``,
+        ``seeds``, ``node_evals``, ``goals`` [m, 3].  ``np.savez(path, **state)`` is a checkpoint.
+        The batch is not modified."""
+        return _forest_export(self.ctx, "b", self.q, queries)
+
+    def import_forest(self, state, queries=None):
+        """Write such a state into the slots ``queries`` (None: 0 .. m - 1) of this batch — of any
+        size, on the same scene, step size and max_iter; the other slots stay untouched.  The
+        slots then continue exactly as the exported ones would have.  Validated as a whole first
+        (parents must precede their children); a refused call raises PPError with ``bad_query``
+        and changes nothing."""
+        _forest_import(self.ctx, "b", state, queries)
+
+    def reset_queries(self, queries, starts, seeds, goals):
+        """Recycle slots: new queries (start pose, seed, goal) in ``queries``, as ``pp_batch_new``
+        would have set them up, while every other query keeps its tree and its progress."""
+        _forest_import(self.ctx, "b", _forest_roots("b", starts, seeds, goals), queries)
 
     def close(self):
         self.ctx.close()
@@ -898,6 +1011,32 @@ class RRTStarBatch:
                                        C.byref(tot), length.ctypes.data_as(dp),
                                        ok.ctypes.data_as(u8)))
         return off, np.stack([x[:cap], y[:cap]], axis=1), length, ok.astype(bool)
+
+    # ---- forest export / import (pp_star_forest_export / _import)
+    def export_forest(self, queries=None):
+        """The complete state of the slots ``queries`` (distinct, any order; None: all) in one
+        call, packed on the device: a dict of numpy arrays — ``off`` int64[m + 1] (slot i's tree
+        is rows off[i]:off[i + 1]), rows ``x``, ``y``, ``yaw``, ``parent``, ``cost``,
+        ``edge_cost``, per slot ``iterations``, ``seeds``, ``node_evals``, ``rewires``,
+        ``focus_xy`` [m, 2], ``focus_bound`` (inf: no focus), ``skipped``.
+        ``np.savez(path, **state)`` is a checkpoint.  The batch is not modified."""
+        return _forest_export(self.ctx, "s", self.q, queries)
+
+    def import_forest(self, state, queries=None):
+        """Write such a state into the slots ``queries`` (None: 0 .. m - 1) of this batch — of any
+        size, on the same scene, step size, max_iter, k and eta; the other slots stay untouched.
+        Under further extend / plan / focus / prune calls the slots evolve exactly as the exported
+        ones would have, bit for bit.  Validated as a whole first: every chain must end in its
+        root, and ``cost`` (may be absent or None: rebuilt) must equal cost[parent] + edge_cost
+        bit for bit.  A refused call raises PPError with ``bad_query`` and changes nothing.  The
+        edges are trusted: ``revalidate`` after importing trees grown in another scene."""
+        _forest_import(self.ctx, "s", state, queries)
+
+    def reset_queries(self, queries, starts, seeds):
+        """Recycle slots: new queries (start pose with its yaw, seed) in ``queries``, as
+        ``pp_star_new`` would have set them up — a root, no iterations, evaluations, rewires or
+        skipped draws, no focus — while every other query keeps its tree and its progress."""
+        _forest_import(self.ctx, "s", _forest_roots("s", starts, seeds), queries)
 
     def close(self):
         self.ctx.close()
