@@ -48,7 +48,10 @@ extern "C" {
  * 5 (+): pp_star_prune added, nothing else changed
  * 5 (+): pp_forest_state, pp_star_forest_export / pp_star_forest_import and
  *        pp_batch_forest_export / pp_batch_forest_import added (the complete state of a set of
- *        query slots out of a batch and into one), nothing else changed */
+ *        query slots out of a batch and into one), nothing else changed
+ * 5 (+): pp_path_segments, pp_star_path_segments / pp_batch_path_segments and
+ *        pp_segments_sample added (planned paths as Dubins segments, sampled into
+ *        trajectories), nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -569,6 +572,65 @@ int pp_star_path(pp_ctx* ctx, int query, const double goal[3], int32_t node, dou
  * outside its query's tree.  The trees are not modified. */
 int pp_star_paths(pp_ctx* ctx, const double* goals, const int32_t* nodes, int64_t* off, double* x,
                   double* y, int64_t cap, int64_t* n_total, double* length, uint8_t* ok);
+
+/* ------------------------------ segment export and sampling (build-defined) */
+/* A planned path as what it is: a chain of Dubins edges, each three primitives (arc / straight /
+ * arc) — with heading and curvature, exact, a few dozen records a path — and a sampler that turns
+ * such rows into trajectories at a spacing of the caller's choosing (CPU restatement:
+ * tests/path_segments_ref.py).
+ * Caller-owned SoA arrays of segments.  size = sizeof(pp_path_segments) as the caller compiled it;
+ * fields past it read as NULL (like pp_forest_state). */
+typedef struct pp_path_segments {
+    uint64_t size;
+    double *x, *y, *yaw; /* the segment's start pose */
+    double *kappa;       /* signed curvature: +1/R (L), 0 (S), -1/R (R); R = the Space's turn radius */
+    double *len;         /* arc length in length units, >= 0 */
+} pp_path_segments;
+/* Row i = the chain of Dubins edges pp_star_paths walks for (query i, goals[3i..], nodes[i]):
+ * goal -> node -> parent -> ... -> root, every edge from the child's stored pose, its word the
+ * one the point export chooses.  Every edge gives exactly three segments (zero-length ones
+ * included), so a row of E edges has 3 E segments and off (q + 1 entries) counts segments.  For an
+ * edge a -> b with word w and (t, p, q): segment 0 starts at a's pose bit for bit; len[j] =
+ * (t | p | q) * R; kappa[j] by w's mode table; segment j + 1 starts at the closed-form end of
+ * segment j in f64 — S: x + len cos(yaw), y + len sin(yaw), yaw; L / R: x + (sin(yaw + kappa len)
+ * - sin(yaw)) / kappa, y - (cos(yaw + kappa len) - cos(yaw)) / kappa, yaw + kappa len.  Yaw is
+ * never wrapped, and the next edge starts from its own stored pose again.
+ * reverse = 0: generation order (the crate's stored yaws point toward the parent: goal edge first,
+ * goal -> root).  reverse = 1: the same curve from the root to the goal, pp_star_paths' row order:
+ * the segments in reverse order, each starting at its own end pose with yaw = end yaw + pi
+ * (unwrapped), kappa negated, len unchanged.  Any other value: PP_ERR_INVALID_ARGUMENT.
+ * length (q, may be NULL): the sum of the row's len in row order, 0 for an empty row; filled with
+ * the segments (not by a sizes-only call).  ok, the empty rows (-1, a goal edge without a word),
+ * PP_ERR_REFERENCE_PANIC and the 8192-deep chain limit: as pp_star_paths.  Sizes-only protocol as
+ * there: seg NULL or cap <= 0 fills off / ok / n_total, PP_OK; cap < *n_total (cap: the entries
+ * each array holds) is PP_ERR_CAPACITY with the sizes filled; a NULL array inside *seg is simply
+ * not written.  PP_ERR_STATE without an RRT* batch or a scene; PP_ERR_INVALID_ARGUMENT for a NULL
+ * goals, nodes, off or n_total, a non-finite goal or a node outside its tree, all checked on the
+ * host before any launch.  No Space::verify is repeated.  Nothing in the batch is modified. */
+int pp_star_path_segments(pp_ctx* ctx, const double* goals, const int32_t* nodes, int reverse,
+                          int64_t* off, const pp_path_segments* seg, int64_t cap,
+                          int64_t* n_total, double* length, uint8_t* ok);
+/* The same for the extend batch: row i = finalize's chain of check_finish(nodes[i]) on query i's
+ * tree with its goal — the goal, optimize's copies (their yaw by compute_yaw), the tree path down
+ * to the root — as pp_batch_paths walks it; ok and the empty rows as there (a finish that does not
+ * verify: ok 0, an empty row). */
+int pp_batch_path_segments(pp_ctx* ctx, const int32_t* nodes, int reverse, int64_t* off,
+                           const pp_path_segments* seg, int64_t cap, int64_t* n_total,
+                           double* length, uint8_t* ok);
+/* Sample q rows of segments (row r = entries [off[r], off[r + 1]) of the five arrays of *seg) every
+ * ds along the arc; a pure function of its arguments: a context, but no scene or batch.  With P_0
+ * = 0, P_{j+1} = P_j + len[j] in row order and L = the last P: samples at s_i = i ds for i = 0 ..
+ * floor(L / ds), and one more at s = L when L > the last s_i; a row without segments has none.  A
+ * sample lies on the first segment j with s < P_{j+1} at u = s - P_j, else on the last segment at
+ * u = len; x, y, yaw by the closed forms above at u, kappa the segment's, s the arc position (each
+ * output may be NULL).  poff (q + 1 entries) counts samples; sizes-only and capacity protocol as
+ * above (every output NULL or cap <= 0: poff and n_total only); more than 2^26 samples in one
+ * call is PP_ERR_CAPACITY.  PP_ERR_INVALID_ARGUMENT, checked on the host: q < 0, a NULL off, seg,
+ * poff, n_total or segment array, off[0] != 0 or off decreasing, a non-finite entry, a negative
+ * len, ds not finite or <= 0.  The arrays are uploaded once and the samples copied back once. */
+int pp_segments_sample(pp_ctx* ctx, int q, const int64_t* off, const pp_path_segments* seg,
+                       double ds, int64_t* poff, double* x, double* y, double* yaw, double* kappa,
+                       double* s, int64_t cap, int64_t* n_total);
 
 /* ------------------------------------- forest export / import (build-defined) */
 /* The complete state of m query slots of a batch, packed: what a checkpoint, a move of a query to

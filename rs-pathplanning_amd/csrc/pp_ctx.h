@@ -12,6 +12,7 @@
 //   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
 //   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
 //   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
+//   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_segments_sample
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -312,6 +313,19 @@ struct PathExport {
 // the most points one export call stages on the device (x and y: 16 B a point, 1 GiB)
 constexpr int64_t kPathsMaxPoints = (int64_t)1 << 26;
 
+// ---- segment export and sampling (pp_*_path_segments, pp_segments_sample: SegArgs,
+// SegSampleArgs), sized to the call: the ancestor paths and the spill list of the export's waves,
+// the packed segment rows (the export's staging, the sampler's input), the sampler's per-row
+// values and its packed samples
+struct SegExport {
+    DBuf<int> path, spill;
+    DBuf<double> x, y, yaw, kappa, len;
+    DBuf<int64_t> off, nfull, cnt, poff;
+    DBuf<double> P, rowlen, sx, sy, syaw, skappa, ss;
+};
+// the most samples one pp_segments_sample call stages on the device
+constexpr int64_t kSegMaxSamples = (int64_t)1 << 26;
+
 // ---- a forest of per-query SoA trees: the host side of MqDev's shared part, under both the
 // extend batch (config 3) and the RRT* batch (config 5).  Tree q lives in rows [q * cap, q * cap +
 // n[q]); the forest runs as nsub sub-batches of consecutive queries, each on its own stream.
@@ -497,6 +511,7 @@ struct pp_ctx {
     ppamd::Batch batch;
     ppamd::StarBatch star;
     ppamd::PathExport paths;
+    ppamd::SegExport seg;
     ppamd::Reval reval;
     ppamd::ForestIo fio;
     ppamd::Profiling prof;
@@ -535,6 +550,11 @@ int paths_items(pp_ctx* c, const Forest& f, const int32_t* nodes, int* k);
 int paths_sizes(pp_ctx* c, int Q, int64_t* off, const double* x, const double* y, int64_t cap,
                 int64_t* n_total, uint8_t* ok, bool* go);
 int paths_line_buffers(pp_ctx* c, int k, CfLines& lines);
+// pp_batch_paths' check_finish step, shared with pp_batch_path_segments (pp_segments.cpp): the
+// batch's goals to the device (batch.goal_d) and check_finish of the k items of paths_items —
+// every item's verdict in paths.ok, its line's point count in paths.cnt, and a line item per
+// verified finish (its optimize chain) in cf.items
+int paths_batch_finish(pp_ctx* c, int k);
 int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines,
                 const int* items, int k, bool star, double* x, double* y, int64_t total,
                 double* len_host = nullptr);

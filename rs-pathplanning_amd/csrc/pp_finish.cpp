@@ -463,6 +463,24 @@ int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines
     return cf_error(err);
 }
 
+int paths_batch_finish(pp_ctx* ctx, int k) {
+    Batch& b = ctx->batch;
+    PathExport& pe = ctx->paths;
+    const int Q = b.f.Q;
+    // check_finish of the k items: every item's verdict, optimize chain (a line item per verified
+    // finish, cf.items) and, from its line pass, the line's point count
+    PP_HIP(b.goal_d.reserve(3 * (size_t)Q));
+    PP_HIP(hipMemcpyAsync(b.goal_d.p, b.goal.data(), 3 * (size_t)Q * sizeof(double),
+                          hipMemcpyHostToDevice, ctx->stream));
+    CfBatch cb;
+    cb.qidx = pe.qidx.p;
+    cb.row_cap = b.f.cap;
+    cb.goals = b.goal_d.p;
+    cb.blocked = b.f.blocked_dev();
+    return cf_run(ctx, b.f.tree_dev(), pe.nodes.p, k, 1, kCfGrid, CfGoal{0.0, 0.0, 0.0, 0.0},
+                  CfOut{pe.ok.p, pe.len.p, pe.cnt.p, nullptr}, cb);
+}
+
 }  // namespace ppamd
 
 extern "C" {
@@ -475,7 +493,6 @@ int pp_batch_paths(pp_ctx* ctx, const int32_t* nodes, int64_t* off, double* x, d
     if (!b.valid) return set_err(PP_ERR_STATE, "pp_batch_new has not been called");
     if (!nodes || !off || !n_total) return set_err(PP_ERR_INVALID_ARGUMENT, "null nodes, off or n_total");
     const int Q = b.f.Q;
-    hipStream_t st = ctx->stream;
     PathExport& pe = ctx->paths;
     int k = 0;
     if ((r = paths_items(ctx, b.f, nodes, &k))) return r;
@@ -485,20 +502,8 @@ int pp_batch_paths(pp_ctx* ctx, const int32_t* nodes, int64_t* off, double* x, d
         if (ok) std::fill(ok, ok + Q, (uint8_t)0);
         return PP_OK;
     }
-    // check_finish of the k items: every item's verdict, optimize chain (a line item per verified
-    // finish, cf.items) and, from its line pass, the line's point count
-    PP_HIP(b.goal_d.reserve(3 * (size_t)Q));
-    PP_HIP(hipMemcpyAsync(b.goal_d.p, b.goal.data(), 3 * (size_t)Q * sizeof(double),
-                          hipMemcpyHostToDevice, st));
-    CfBatch cb;
-    cb.qidx = pe.qidx.p;
-    cb.row_cap = b.f.cap;
-    cb.goals = b.goal_d.p;
-    cb.blocked = b.f.blocked_dev();
+    if ((r = paths_batch_finish(ctx, k))) return r;
     const TreeDev tr = b.f.tree_dev();
-    if ((r = cf_run(ctx, tr, pe.nodes.p, k, 1, kCfGrid, CfGoal{0.0, 0.0, 0.0, 0.0},
-                    CfOut{pe.ok.p, pe.len.p, pe.cnt.p, nullptr}, cb)))
-        return r;
     bool go = false;
     if ((r = paths_sizes(ctx, Q, off, x, y, cap, n_total, ok, &go)) || !go) return r;
     CfLines lines;

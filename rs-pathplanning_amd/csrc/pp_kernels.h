@@ -225,6 +225,69 @@ hipError_t launch_paths(hipStream_t st, const SceneDev& sc, const PathsArgs& a,
 hipError_t launch_paths_scan(hipStream_t st, int Q, const int* slot, const int* okf,
                              const int* cnt, int64_t* off, uint8_t* okq);
 
+// Segment export (pp_star_path_segments / pp_batch_path_segments, pp_k_segments.hip; DESIGN.md
+// §3.7 "Segment export and sampling"): the chains of the same line items as arc / straight / arc
+// records, three per Dubins edge, packed.  The count pass (write = false) stores cnt[b] = 3 E
+// (star: and okf[b], 0 with cnt 0 when the goal edge has no word); the write pass stores row q =
+// [off[q], off[q + 1]) of the five arrays (a null one is skipped), generation order or, reverse,
+// the same curve from the root.  One wave per item with a path_cap-deep ancestor path each (path:
+// grid x path_cap ints); spill != null: a deeper chain is appended to spill (the items layout,
+// spill[0] zeroed before the launch) for a launch at the full depth.  err bits as check_finish's
+// (1 depth, 2 an edge without a word) and 16: a row's size differs from the count pass.
+struct SegArgs {
+    TreeDev tr{};
+    int row_cap = 0;
+    const int* qidx = nullptr;
+    const int* nodes = nullptr;
+    const double* goals = nullptr;  // [3Q] (gx, gy, gyaw)
+    double turn_radius = 1.0;
+    int reverse = 0;
+    const int64_t* off = nullptr;   // [Q + 1]
+    double* ox = nullptr;
+    double* oy = nullptr;
+    double* oyaw = nullptr;
+    double* okappa = nullptr;
+    double* olen = nullptr;
+    int* cnt = nullptr;
+    int* okf = nullptr;
+    int* path = nullptr;
+    int path_cap = 0;
+    int* spill = nullptr;
+    int spill_cap = 0;
+};
+hipError_t launch_segments(hipStream_t st, const SegArgs& a, int grid, int* err, const int* items,
+                           int items_cap, bool star, bool write);
+// The sampler (pp_segments_sample).  Prefix: per row r = segments [off[r], off[r + 1]) the
+// running arc position P[j] = len[off[r]] + ... + len[j] added in row order, the row's length
+// rowlen[r], nfull[r] = floor(rowlen / ds) (clamped to max_samples) and its sample count cnt[r]
+// (nfull + 1, one more when rowlen > nfull * ds; 0 for a row without segments).  Sample: output i
+// of row r (poff[r] <= i < poff[r + 1]) at s = k ds (k = i - poff[r] <= nfull[r]) or rowlen[r],
+// on the first segment with s < P[j] or the last at its end; a null output is skipped.
+struct SegSampleArgs {
+    int q = 0;
+    double ds = 1.0;
+    int64_t max_samples = 0;
+    const int64_t* off = nullptr;
+    const double* x = nullptr;
+    const double* y = nullptr;
+    const double* yaw = nullptr;
+    const double* kappa = nullptr;
+    const double* len = nullptr;
+    double* P = nullptr;
+    double* rowlen = nullptr;
+    int64_t* nfull = nullptr;
+    int64_t* cnt = nullptr;
+    const int64_t* poff = nullptr;  // [q + 1]
+    int64_t total = 0;              // poff[q]
+    double* sx = nullptr;
+    double* sy = nullptr;
+    double* syaw = nullptr;
+    double* skappa = nullptr;
+    double* ss = nullptr;
+};
+hipError_t launch_segments_prefix(hipStream_t st, const SegSampleArgs& a);
+hipError_t launch_segments_sample(hipStream_t st, const SegSampleArgs& a);
+
 // pp_batch_plan: the (query, node) items of the accepted nodes (off: [Q + 1] exclusive scan of
 // n_q - 1), and per query the first minimum length over its items' check_finish results
 hipError_t launch_mq_plan_items(hipStream_t s, int Q, const int* off, int* qidx, int* nodes);

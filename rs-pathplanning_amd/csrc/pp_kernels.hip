@@ -40,6 +40,7 @@ __device__ __noinline__ int s_classify_poly(const SceneDev& sc, double ax, doubl
                                             double by, double t_lo, double t_hi, double dl);
 }  // namespace ppamd
 
+#include "pp_chain_dev.h"
 #include "pp_steer_dev.h"
 #include "pp_steer_launch.h"
 
@@ -1805,9 +1806,7 @@ __global__ __launch_bounds__(kResolveThreads) void resolve_tail_kernel(WinKArgs 
 //                               reference's panic (rrt.rs:529).
 //   length                      verified finishes: the edges' literal Dubins points, then
 //                               euclidean_length of the reversed line summed in line order.
-struct CfPose {
-    double x, y, yaw;
-};
+// (CfPose, cf_path and the pose providers: pp_chain_dev.h)
 constexpr int kCfThreads = 64 * kCfWaves;
 
 __device__ inline bool same_pose(const CfPose& a, const CfPose& b) {
@@ -1950,33 +1949,6 @@ __device__ inline void cf_node_setup(const TreeDev& tr_in, const CfBatch& cb, in
         if (gtab && *gtab) *gtab += m;
     }
 }
-
-// A node's ancestor path root first into path[0, D) (NodeIter, rrt.rs:253-265, reversed), by the
-// calling wave (lane 0 follows the parents, then the lanes reverse it); -1 past kCfMaxDepth.
-__device__ inline int cf_path(const TreeDev& tr, int node, int* __restrict__ path,
-                              int cap = kCfMaxDepth) {
-    const int lane = __lane_id();
-    int d = 0;
-    if (lane == 0) {
-        int c = node;
-        while (c >= 0 && d < cap) {
-            path[d++] = c;
-            c = tr.parent[c];
-        }
-        if (c >= 0) d = -1;
-    }
-    d = __shfl(d, 0);
-    __builtin_amdgcn_wave_barrier();
-    if (d > 0)
-        for (int i = lane; i < d / 2; i += 64) {
-            const int t = path[i];
-            path[i] = path[d - 1 - i];
-            path[d - 1 - i] = t;
-        }
-    __builtin_amdgcn_wave_barrier();
-    return d;
-}
-
 
 __global__ __launch_bounds__(kCfThreads, kCfMinW) void check_finish_kernel(
     const SceneDev* __restrict__ scg, TreeDev tr_in, const int* __restrict__ nodes, int k, double gx_in, double gy_in,
@@ -2691,12 +2663,8 @@ hipError_t launch_check_finish(hipStream_t st, const SceneDev& sc, const SceneDe
 // ------------------------------------------- packed line export (pp_batch_paths, pp_star_paths)
 //
 // Every query's line in one CSR buffer, root side first.  The line generation is one template
-// over a pose provider — the chain of poses whose consecutive pairs are the line's Dubins edges:
-//   CfChainPoses    finalize's chain (check_finish_kernel's pose(j)): the goal, optimize's copies,
-//                   the tree path down to the root; the root contributes no point
-//   StarChainPoses  pp_star_path's chain: the goal with its own yaw, then the stored poses of the
-//                   node, its parent, ..., the root (a rewired node keeps its pose, so no edge
-//                   uses compute_yaw); the root's point ends the forward line
+// over a pose provider — the chain of poses whose consecutive pairs are the line's Dubins edges
+// (CfChainPoses, StarChainPoses: pp_chain_dev.h).
 // line_gen runs cf_line_kernel's steps for such a chain on one wave — every edge's word and slot
 // count (cf_npoint_steer, a lane per edge), the slot offsets, the literal points edge by edge
 // (line_edge_wave) into the workgroup's staging, forward order — and paths_kernel either counts
@@ -2704,52 +2672,6 @@ hipError_t launch_check_finish(hipStream_t st, const SceneDev& sc, const SceneDe
 // forward point f of npts goes to row[npts - 1 - f], a lane per point of an edge, so consecutive
 // lanes store consecutive addresses.  Items, tiers and the spill list are cf_line_kernel's.
 enum : int { kLgNone = -2, kLgCap = -1, kLgOverflow = -4, kLgNoneGoal = -5 };
-
-struct CfChainPoses {
-    static constexpr bool kRootPoint = false;  // finalize: the root contributes no point
-    static constexpr bool kGoalNoneOk = false;
-    TreeDev tr;
-    const int* path;
-    const int* pos;
-    int D, s, ps;
-    double gx, gy, gyaw;
-    __device__ CfChainPoses(const TreeDev& t, const int* path_, int D_, const int* o,
-                            const int* pos_, const double* goal)
-        : tr(t), path(path_), pos(pos_), D(D_), s(o[1]), gx(goal[0]), gy(goal[1]), gyaw(goal[2]) {
-        ps = s > 0 ? pos[s - 1] : D - 1;
-    }
-    __device__ int edges() const { return 1 + s + ps; }
-    __device__ CfPose pose(int j) const {
-        if (j == 0) return CfPose{gx, gy, gyaw};  // (a batch's goal: gyaw_opt == gyaw)
-        if (j <= s) {
-            const int i = j - 1;
-            const int here = path[i == 0 ? D - 1 : pos[i - 1]];
-            const int to = path[pos[i]];
-            const double x = tr.x[here], y = tr.y[here];
-            return CfPose{x, y, atan2(tr.y[to] - y, tr.x[to] - x)};  // Node::new (compute_yaw)
-        }
-        const int node = path[ps - (j - s - 1)];
-        return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
-    }
-};
-
-struct StarChainPoses {
-    static constexpr bool kRootPoint = true;
-    static constexpr bool kGoalNoneOk = true;  // a goal edge without a word: ok 0, an empty row
-    TreeDev tr;
-    const int* path;
-    int D;
-    double gx, gy, gyaw;
-    __device__ StarChainPoses(const TreeDev& t, const int* path_, int D_, const int*, const int*,
-                              const double* goal)
-        : tr(t), path(path_), D(D_), gx(goal[0]), gy(goal[1]), gyaw(goal[2]) {}
-    __device__ int edges() const { return D; }  // the goal edge, then node -> parent down to the root
-    __device__ CfPose pose(int j) const {
-        if (j == 0) return CfPose{gx, gy, gyaw};
-        const int node = path[D - j];
-        return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
-    }
-};
 
 // The chain's line by the calling wave (all 64 lanes of a one-wave workgroup): the edges' points
 // in forward order in px / py, et[2e] / et[2e + 1] = edge e's offset there and kept count; pyw

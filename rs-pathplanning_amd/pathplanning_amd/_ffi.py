@@ -50,6 +50,7 @@ EXPORTED = [
     "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export", "pp_star_revalidate",
     "pp_star_repair", "pp_star_set_focus", "pp_star_get_focus", "pp_star_prune",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
+    "pp_star_path_segments", "pp_batch_path_segments", "pp_segments_sample",
     "pp_star_forest_export", "pp_star_forest_import", "pp_batch_forest_export",
     "pp_batch_forest_import",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
@@ -102,6 +103,15 @@ class ForestStateC(C.Structure):
         ("focus_xy", C.POINTER(C.c_double)), ("focus_bound", C.POINTER(C.c_double)),
         ("skipped", C.POINTER(C.c_int64)), ("goals", C.POINTER(C.c_double)),
     ]
+
+
+class PathSegmentsC(C.Structure):
+    """pp_path_segments: caller-owned SoA arrays of segments, ``size`` first."""
+    _fields_ = [("size", C.c_uint64)] + [(n, C.POINTER(C.c_double))
+                                         for n in ("x", "y", "yaw", "kappa", "len")]
+
+
+SEGMENT_FIELDS = ("x", "y", "yaw", "kappa", "len")
 
 
 # the arrays of a forest state dict (RRTStarBatch / RRTBatch export_forest): dtype, entries per
@@ -219,6 +229,12 @@ def lib():
             "pp_star_path": ([vp, C.c_int, dp, C.c_int32, dp, dp, C.c_int64, i64p, dp], C.c_int),
             "pp_star_paths": ([vp, dp, ip, i64p, dp, dp, C.c_int64, i64p, dp,
                                C.POINTER(C.c_uint8)], C.c_int),
+            "pp_star_path_segments": ([vp, dp, ip, C.c_int, i64p, C.POINTER(PathSegmentsC),
+                                       C.c_int64, i64p, dp, C.POINTER(C.c_uint8)], C.c_int),
+            "pp_batch_path_segments": ([vp, ip, C.c_int, i64p, C.POINTER(PathSegmentsC),
+                                        C.c_int64, i64p, dp, C.POINTER(C.c_uint8)], C.c_int),
+            "pp_segments_sample": ([vp, C.c_int, i64p, C.POINTER(PathSegmentsC), C.c_double, i64p,
+                                    dp, dp, dp, dp, dp, C.c_int64, i64p], C.c_int),
             "pp_star_forest_export": ([vp, ip, C.c_int, C.POINTER(ForestStateC), C.c_int64, i64p],
                                       C.c_int),
             "pp_star_forest_import": ([vp, ip, C.c_int, C.POINTER(ForestStateC), ip], C.c_int),

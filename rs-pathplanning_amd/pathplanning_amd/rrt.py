@@ -567,6 +567,67 @@ def _forest_roots(kind, starts, seeds, goals=None):
     return st
 
 
+def _segments_struct(seg):
+    """A PathSegmentsC over the five arrays of ``seg`` (float64, contiguous; a missing or None
+    entry: NULL), and the arrays it points into."""
+    st = _ffi.PathSegmentsC()
+    st.size = C.sizeof(st)
+    keep = {}
+    for name in _ffi.SEGMENT_FIELDS:
+        a = seg.get(name)
+        if a is None:
+            continue
+        keep[name] = np.ascontiguousarray(a, dtype=np.float64)
+        setattr(st, name, keep[name].ctypes.data_as(C.POINTER(C.c_double)))
+    return st, keep
+
+
+def _path_segments(q, call):
+    """The two-call protocol of pp_star_path_segments / pp_batch_path_segments: ``call(off, seg,
+    cap, tot, length, ok)`` binds everything in front of ``off``."""
+    i64, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    off = np.zeros(q + 1, dtype=np.int64)
+    ok = np.zeros(q, dtype=np.uint8)
+    length = np.zeros(q)
+    tot = C.c_int64(0)
+    okp = ok.ctypes.data_as(C.POINTER(C.c_uint8))
+    _ffi.check(call(off.ctypes.data_as(i64), None, 0, C.byref(tot), None, okp))
+    cap = tot.value
+    seg = {name: np.zeros(cap) for name in _ffi.SEGMENT_FIELDS}
+    if cap > 0:
+        st, _ = _segments_struct(seg)
+        _ffi.check(call(off.ctypes.data_as(i64), C.byref(st), cap, C.byref(tot),
+                        length.ctypes.data_as(dp), okp))
+    return off, seg, length, ok.astype(bool)
+
+
+def sample_segments(ctx, off, seg, ds):
+    """Sample rows of Dubins segments every ``ds`` along the arc (pp_segments_sample): row r =
+    entries ``off[r]:off[r + 1]`` of the five arrays of the dict ``seg`` (``path_segments``'
+    output, or hand-built).  Samples at s = 0, ds, 2 ds, ... and one more at the row's end when
+    that is past the last; position and yaw by the segments' closed forms (yaw unwrapped), the
+    segment's curvature.  Returns (poff int64[q + 1], x, y, yaw, kappa, s): row r's samples are
+    ``[poff[r]:poff[r + 1]]``.  A pure function of its arguments; ``ctx``: any context."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    q = len(off) - 1
+    st, keep = _segments_struct(seg)
+    i64, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    poff = np.zeros(q + 1, dtype=np.int64)
+    tot = C.c_int64(0)
+    L = _ffi.lib()
+    _ffi.check(L.pp_segments_sample(ctx.handle, q, off.ctypes.data_as(i64), C.byref(st),
+                                    float(ds), poff.ctypes.data_as(i64), None, None, None, None,
+                                    None, 0, C.byref(tot)))
+    cap = tot.value
+    out = [np.zeros(cap) for _ in range(5)]
+    if cap > 0:
+        _ffi.check(L.pp_segments_sample(ctx.handle, q, off.ctypes.data_as(i64), C.byref(st),
+                                        float(ds), poff.ctypes.data_as(i64),
+                                        *[a.ctypes.data_as(dp) for a in out], cap, C.byref(tot)))
+    del keep
+    return (poff, *out)
+
+
 class RRTBatch:
     """Many independent planners on one scene (BASELINE config 3): ``RRT::new`` per query
     (rrt.rs:335-355) with its own start, goal and sampling stream, advanced in lockstep — one
@@ -701,6 +762,28 @@ class RRTBatch:
                                         y.ctypes.data_as(dp), cap, C.byref(tot),
                                         ok.ctypes.data_as(u8)))
         return off, np.stack([x[:tot.value], y[:tot.value]], axis=1), ok.astype(bool)
+
+    def path_segments(self, nodes=None, reverse=False):
+        """The rows of ``paths(nodes)`` as Dubins segments (pp_batch_path_segments): every edge of
+        finalize's chain as three arc / straight / arc records.  Returns (off int64[q + 1], seg,
+        length float64[q], ok bool[q]): ``seg`` a dict of float64 arrays ``x``, ``y``, ``yaw``
+        (the segment's start pose, yaw unwrapped), ``kappa`` (signed curvature) and ``len``; row q
+        = entries ``off[q]:off[q + 1]``, three per edge, in generation order (goal edge first,
+        headings as stored) or, ``reverse``, the same curve from the root to the goal (``paths``'
+        order).  ``nodes`` as in ``paths``."""
+        if nodes is None:
+            self.last_plan = self.plan()
+            nodes = self.last_plan["best_node"]
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+        L, h, ip = _ffi.lib(), self.ctx.handle, C.POINTER(C.c_int32)
+        return _path_segments(self.q, lambda *a: L.pp_batch_path_segments(
+            h, nodes.ctypes.data_as(ip), int(bool(reverse)), *a))
+
+    def trajectories(self, ds, nodes=None, reverse=True):
+        """``path_segments(nodes, reverse)`` sampled every ``ds`` (``sample_segments``): (poff, x,
+        y, yaw, kappa, s), root to goal by default."""
+        off, seg, _, _ = self.path_segments(nodes, reverse)
+        return sample_segments(self.ctx, off, seg, ds)
 
     def tree(self, query: int, n: int | None = None):
         """(x, y, yaw, parent) of one query's tree, root first (``n``: its size, when known)."""
@@ -1011,6 +1094,34 @@ class RRTStarBatch:
                                        C.byref(tot), length.ctypes.data_as(dp),
                                        ok.ctypes.data_as(u8)))
         return off, np.stack([x[:cap], y[:cap]], axis=1), length, ok.astype(bool)
+
+    def path_segments(self, goals, nodes=None, reverse=False):
+        """The rows of ``paths(goals, nodes)`` as Dubins segments (pp_star_path_segments): every
+        edge of the chain goal -> node -> parent -> ... -> root as three arc / straight / arc
+        records, generated on the device.  Returns (off int64[q + 1], seg, length float64[q],
+        ok bool[q]): ``seg`` a dict of float64 arrays ``x``, ``y``, ``yaw`` (the segment's start
+        pose, yaw unwrapped), ``kappa`` (signed curvature, +-1 / turn radius or 0) and ``len``;
+        row q = entries ``off[q]:off[q + 1]``, three per edge, in generation order (goal edge
+        first, headings as stored: toward the root) or, ``reverse``, the same curve from the root
+        to the goal (``paths``' order).  ``length[q]``: the sum of the row's ``len``;
+        ``length / turn_radius`` is ``plan``'s cost for its best node.  ``goals``, ``nodes``,
+        ``ok`` and the empty rows as in ``paths``."""
+        g = np.asarray(goals, dtype=np.float64)
+        g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
+        g = np.ascontiguousarray(g, dtype=np.float64).reshape(self.q, 3)
+        if nodes is None:
+            nodes = self.plan(g)[0]
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+        L, h = _ffi.lib(), self.ctx.handle
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        return _path_segments(self.q, lambda *a: L.pp_star_path_segments(
+            h, g.ctypes.data_as(dp), nodes.ctypes.data_as(ip), int(bool(reverse)), *a))
+
+    def trajectories(self, goals, ds, nodes=None, reverse=True):
+        """``path_segments(goals, nodes, reverse)`` sampled every ``ds`` (``sample_segments``):
+        (poff, x, y, yaw, kappa, s), root to goal by default."""
+        off, seg, _, _ = self.path_segments(goals, nodes, reverse)
+        return sample_segments(self.ctx, off, seg, ds)
 
     # ---- forest export / import (pp_star_forest_export / _import, DESIGN.md §3.9)
     def export_forest(self, queries=None):
