@@ -1,5 +1,5 @@
-// pp_kernels.h — host-side launch wrappers of the HIP kernels (pp_kernels.hip; the API kernels'
-// wrappers: pp_k_steer.hip).
+// pp_kernels.h — host-side launch wrappers of the HIP kernels, the one header of them that the
+// host side includes.  A section that names no unit is implemented in pp_kernels.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 
 namespace ppamd {
 
+// The window pipeline (pp_k_window.hip).
 // Everything one window (or one nearest-neighbour batch) touches.  Buffers are sized for K.
 struct WindowArgs {
     int K = 0;           // samples per window
@@ -74,6 +75,7 @@ hipError_t launch_drain(hipStream_t s, const WindowArgs& a, int64_t seq_next);
 // rescan.
 hipError_t launch_nearest(hipStream_t s, const WindowArgs& a);
 
+// The API kernels (pp_k_steer.hip).
 // Space::verify (rrt.rs:124-137) of k polylines, line i = points [off[i], off[i + 1]) of X/Y;
 // ok[i] = 1 when it verifies.
 hipError_t launch_verify_lines(hipStream_t st, const SceneDev& sc, const double* X,
@@ -83,6 +85,7 @@ hipError_t launch_steer_tasks(hipStream_t st, const SceneDev& sc, const TreeDev&
                               const SteerTask* tasks, int n, int* out_status, double* out_yaw,
                               double* scratch);
 
+// check_finish, the packed line export and the batch plan's rounds (pp_kernels.hip).
 // RRT::check_finish for k tree nodes (one wave per node, at most `grid` workgroups of kCfWaves
 // waves; gpath: grid * kCfWaves * kCfMaxDepth ints, the waves' ancestor paths).  ok/len/npts per
 // node; chain (optional) = k rows of [levels, edges, optimize's chosen ancestors...] with
@@ -523,6 +526,7 @@ hipError_t launch_forest_validate(hipStream_t s, const ForestIoArgs& a);
 // the staged rows and per-slot values into the forest, and the slots' derived state
 hipError_t launch_forest_scatter(hipStream_t s, const ForestIoArgs& a);
 
+// The Dubins API kernels (pp_k_steer.hip).
 // dubins_path_planning_from_origin for n (dx, dy, eyaw, c, step_size) configurations
 hipError_t launch_dubins_origin(hipStream_t st, const double* conf, int n, int cap, double* px,
                                 double* py, double* pyaw, int* n_out, int* word_out,
