@@ -51,7 +51,9 @@ extern "C" {
  *        query slots out of a batch and into one), nothing else changed
  * 5 (+): pp_path_segments, pp_star_path_segments / pp_batch_path_segments and
  *        pp_segments_sample added (planned paths as Dubins segments, sampled into
- *        trajectories), nothing else changed */
+ *        trajectories), nothing else changed
+ * 5 (+): pp_star_shortcut, pp_star_shortcut_edges and pp_star_chain_segments added (RRT* paths
+ *        shortened by Dubins shortcuts along the chain), nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -631,6 +633,52 @@ int pp_batch_path_segments(pp_ctx* ctx, const int32_t* nodes, int reverse, int64
 int pp_segments_sample(pp_ctx* ctx, int q, const int64_t* off, const pp_path_segments* seg,
                        double ds, int64_t* poff, double* x, double* y, double* yaw, double* kappa,
                        double* s, int64_t cap, int64_t* n_total);
+
+/* ------------------------------ shortcuts along the chain (build-defined) */
+/* Shorten the path goal -> nodes[i] -> parent -> ... -> root of every query by Dubins shortcuts
+ * between the poses of its own chain (CPU restatement: tests/star_shortcut_ref.py).  Positions:
+ * c_0 = the goal (its own yaw), c_1 = the node, c_2 = its parent, ..., c_D = the root, each with
+ * its stored pose.  Edge (i -> j), i < j <= i + span, is RRT*'s feasible edge from c_i's pose (own
+ * yaw, like a rewire or goal edge) to c_j's stored pose: feasible when the word is Some and
+ * Space::verify accepts the edge's points followed by c_j's point; w(i, j) = its Dubins cost (the
+ * unit of pp_star_tree_export's cost) or +inf.  Every edge, the chain's own included, is
+ * evaluated afresh against the context's current Space.  best[D] = 0; for i = D - 1 .. 0, best[i]
+ * = the first strict minimum in increasing j of best[j] + w(i, j) (each sum rounded once; the
+ * lowest j on an exact tie) and next[i] that j; the path follows next from 0 and costs best[0].
+ * With span 1 on an unchanged scene that is pp_star_plan's total for the node.
+ * goals: q rows (gx, gy, gyaw); nodes: q entries (-1: skip); span in [1, 63].  Row i of chain
+ * (int32, CSR by off, q + 1 entries) = the tree nodes of the shortened path after the goal: the
+ * node the goal now connects to first, 0 (the root) last.  cost[i] = best[0], ok[i] = 1 — or +inf,
+ * 0 and an empty row when nodes[i] is -1 or no feasible route exists within the span (cost, ok:
+ * may be NULL).  *n_tested (may be NULL) = the (i, j) pairs considered.  Sizes-only and capacity
+ * protocol as pp_star_paths: chain NULL or cap <= 0 fills off / cost / ok / n_total / n_tested;
+ * cap < *n_total is PP_ERR_CAPACITY with those filled.  A chain deeper than 8192 nodes, or more
+ * than 2^26 pairs in one call (checked before any steer launch), is PP_ERR_CAPACITY.
+ * PP_ERR_INVALID_ARGUMENT, before any launch: span outside [1, 63], NULL goals, nodes, off or
+ * n_total, a non-finite goal, a node outside its tree.  PP_ERR_STATE without an RRT* batch or a
+ * scene; PP_ERR_STEER_OVERFLOW as pp_star_plan.  Trees, focus, counters and stats are untouched. */
+int pp_star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int span,
+                     int64_t* off, int32_t* chain, int64_t cap, int64_t* n_total, double* cost,
+                     uint8_t* ok, int64_t* n_tested);
+/* The band of one query, un-culled (the counterpart of pp_star_goal_costs): *depth = D; cnode[i - 1]
+ * = the tree node of position i (D entries, may be NULL); w[i * span + (j - i - 1)] = w(i, j) for
+ * i < D, +inf where infeasible or j > D.  cap counts rows of w (and entries of cnode): w NULL
+ * gives the size only, cap < D is PP_ERR_CAPACITY.  Errors as pp_star_shortcut's, and
+ * PP_ERR_INVALID_ARGUMENT for a query out of range or a NULL goal or depth. */
+int pp_star_shortcut_edges(pp_ctx* ctx, int query, const double goal[3], int32_t node, int span,
+                           double* w, int32_t* cnode, int64_t cap, int64_t* depth);
+/* pp_star_path_segments over caller-supplied chains: row i = goal -> chain[coff[i]] -> ... ->
+ * chain[coff[i + 1] - 1] on query i's tree (coff: q + 1 entries, coff[0] = 0, not decreasing) —
+ * pp_star_shortcut's rows, or any chain of tree nodes that ends in the root.  The words, the three
+ * records per edge, reverse, length, ok, the sizes-only protocol and the errors are as there; an
+ * empty chain row gives an empty row with ok 0.  A chain entry outside its tree, a row that does
+ * not end in node 0, a row longer than 8192 nodes or a NULL coff or chain (with coff[q] > 0) is
+ * PP_ERR_INVALID_ARGUMENT, checked on the host against the tree sizes.  No Space::verify is
+ * repeated here.  With pp_segments_sample a shortened path becomes a trajectory. */
+int pp_star_chain_segments(pp_ctx* ctx, const double* goals, const int64_t* coff,
+                           const int32_t* chain, int reverse, int64_t* off,
+                           const pp_path_segments* seg, int64_t cap, int64_t* n_total,
+                           double* length, uint8_t* ok);
 
 /* ------------------------------------- forest export / import (build-defined) */
 /* The complete state of m query slots of a batch, packed: what a checkpoint, a move of a query to

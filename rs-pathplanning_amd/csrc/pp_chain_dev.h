@@ -45,6 +45,7 @@ __device__ inline int cf_path(const TreeDev& tr, int node, int* __restrict__ pat
 //   StarChainPoses  pp_star_path's chain: the goal with its own yaw, then the stored poses of the
 //                   node, its parent, ..., the root (a rewired node keeps its pose, so no edge
 //                   uses compute_yaw); the root's point ends the forward line
+//   CsrChainPoses   the same over a caller-supplied chain of tree nodes (below)
 struct CfChainPoses {
     static constexpr bool kRootPoint = false;  // finalize: the root contributes no point
     static constexpr bool kGoalNoneOk = false;
@@ -87,6 +88,27 @@ struct StarChainPoses {
     __device__ CfPose pose(int j) const {
         if (j == 0) return CfPose{gx, gy, gyaw};
         const int node = path[D - j];
+        return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
+    }
+};
+
+// pp_star_chain_segments' chain: the goal with its own yaw, then the stored poses of the caller's
+// nodes in the caller's order (path[0] the node after the goal, path[D - 1] the root) — a
+// shortened path's edges skip tree nodes, so the chain is given, not walked
+struct CsrChainPoses {
+    static constexpr bool kRootPoint = true;
+    static constexpr bool kGoalNoneOk = true;
+    TreeDev tr;
+    const int* path;
+    int D;
+    double gx, gy, gyaw;
+    __device__ CsrChainPoses(const TreeDev& t, const int* path_, int D_, const int*, const int*,
+                             const double* goal)
+        : tr(t), path(path_), D(D_), gx(goal[0]), gy(goal[1]), gyaw(goal[2]) {}
+    __device__ int edges() const { return D; }
+    __device__ CfPose pose(int j) const {
+        if (j == 0) return CfPose{gx, gy, gyaw};
+        const int node = path[j - 1];
         return CfPose{tr.x[node], tr.y[node], tr.yaw[node]};
     }
 };

@@ -12,7 +12,9 @@
 //   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
 //   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
 //   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
-//   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_segments_sample
+//   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_star_chain_segments,
+//                    pp_segments_sample
+//   pp_shortcut.cpp  pp_star_shortcut, pp_star_shortcut_edges
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -465,6 +467,16 @@ struct ForestIo {
     DBuf<uint8_t> sblocked;
 };
 
+// ---- shortcuts along the chain (pp_star_shortcut / pp_star_shortcut_edges: ShortcutArgs), sized
+// to the call; cchain / coff: pp_star_chain_segments' uploaded chains
+struct Shortcut {
+    DBuf<int> chain, next, depth, plen, err, out, cchain;
+    DBuf<int64_t> npair, pbase, boff, tdst, off, coff;
+    DBuf<double> band, cost;
+};
+// the most (i, j) pairs one pp_star_shortcut call steers
+constexpr int64_t kShortcutMaxPairs = (int64_t)1 << 26;
+
 // ---- profiling
 struct Profiling {
     bool on = false;
@@ -514,6 +526,7 @@ struct pp_ctx {
     ppamd::SegExport seg;
     ppamd::Reval reval;
     ppamd::ForestIo fio;
+    ppamd::Shortcut shortcut;
     ppamd::Profiling prof;
 
     // the scene as the one-tree planner's kernels see it (its step, its blocked root)

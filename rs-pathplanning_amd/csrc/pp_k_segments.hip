@@ -7,6 +7,7 @@
 //                               records serially, stored straight into the packed SoA row (or its
 //                               mirror for reverse).  The count pass only needs E and the None
 //                               flags.  No points, no line buffers, no literal pool.
+//                               (CsrChainPoses: the chain is the caller's, no ancestor path.)
 //   segments_prefix_kernel      one wave per row: the running arc position in row order (serial
 //                               f64 additions, as the restatement's) and the row's sample count
 //   segments_sample_kernel      one thread per sample: its row by binary search in poff, its
@@ -14,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "pp_chain_dev.h"
 #include "pp_device.h"
@@ -82,13 +84,20 @@ __global__ __launch_bounds__(kSegThreads) void segments_kernel(SegArgs a, int* _
         tr.y += ro;
         tr.yaw += ro;
         tr.parent += ro;
-        const int D = cf_path(tr, a.nodes[b], path, a.path_cap);
+        int D;
+        const int* cpath = path;
+        if constexpr (std::is_same<P, CsrChainPoses>::value) {  // the caller's chain, as given
+            cpath = a.cchain + a.coff[q];
+            D = (int)(a.coff[q + 1] - a.coff[q]);
+        } else {
+            D = cf_path(tr, a.nodes[b], path, a.path_cap);
+        }
         __syncthreads();
         if (D < 0) {
             seg_spill(a, o, tid, err);
             continue;
         }
-        const P p(tr, path, D, o, s_pos, a.goals + 3 * (size_t)q);
+        const P p(tr, cpath, D, o, s_pos, a.goals + 3 * (size_t)q);
         const int E = p.edges();
         int64_t base = 0;
         if (kWrite) {
@@ -167,6 +176,8 @@ static hipError_t launch_segments_t(hipStream_t st, const SegArgs& a, int grid, 
 hipError_t launch_segments(hipStream_t st, const SegArgs& a, int grid, int* err, const int* items,
                            int items_cap, bool star, bool write) {
     if (grid <= 0) return hipSuccess;
+    if (star && a.cchain)
+        return launch_segments_t<CsrChainPoses>(st, a, grid, err, items, items_cap, write);
     return star ? launch_segments_t<StarChainPoses>(st, a, grid, err, items, items_cap, write)
                 : launch_segments_t<CfChainPoses>(st, a, grid, err, items, items_cap, write);
 }

@@ -257,6 +257,10 @@ struct SegArgs {
     int path_cap = 0;
     int* spill = nullptr;
     int spill_cap = 0;
+    // caller-supplied chains (pp_star_chain_segments; star only): query q's chain is cchain[coff[q]
+    // .. coff[q + 1]), the node after the goal first and the root last; no ancestor path is walked
+    const int* cchain = nullptr;
+    const int64_t* coff = nullptr;
 };
 hipError_t launch_segments(hipStream_t st, const SegArgs& a, int grid, int* err, const int* items,
                            int items_cap, bool star, bool write);
@@ -356,6 +360,47 @@ struct StarGoalArgs {
     double* total = nullptr;        // q1 == q0 + 1: total[m] of that query's nodes (or null)
 };
 hipError_t launch_star_goal(hipStream_t s, const StarGoalArgs& g, int rounds);
+
+// Shortcuts along the chain (pp_star_shortcut / pp_star_shortcut_edges, pp_k_shortcut.hip;
+// DESIGN.md §3.7 "Shortcuts along the chain").  Item b < k is (query qidx[b], node nodes[b]); its
+// positions are c_0 = the goal, c_i = chain[b * stride + i - 1] for i = 1 .. D = depth[b] (c_1 the
+// node, c_D the root).  Row i < D of its band holds sp = min(span, D) entries, entry l the edge
+// c_i -> c_{i + 1 + l} (entries with i + 1 + l > D are never written or read); its pairs, row by
+// row and l < min(span, D - i), are numbered pbase[b] .. pbase[b + 1] - 1 over the call, and a
+// steer round serves a run of these numbers in the batch `a`'s round-B task arrays (as the goal
+// rounds borrow them: StarGoalArgs).
+struct ShortcutArgs {
+    StarArgs a;
+    int k = 0;
+    int span = 1;
+    const int* qidx = nullptr;      // [k]
+    const int* nodes = nullptr;     // [k]
+    const double* goals = nullptr;  // [3 * queries of the batch] (gx, gy, gyaw)
+    int stride = 0;                 // chain / next entries per item
+    int* chain = nullptr;           // [k * stride]; after the DP: the shortened path's nodes
+    int* next = nullptr;            // [k * stride] the DP's next[i], i < D
+    int* depth = nullptr;           // [k] D; 0: deeper than stride (err |= 1)
+    int64_t* npair = nullptr;       // [k] the item's pairs
+    const int64_t* pbase = nullptr; // [k + 1] exclusive scan of npair
+    const int64_t* boff = nullptr;  // [k + 1] exclusive scan of D * min(span, D): the bands
+    double* band = nullptr;         // w(i, j) or +inf
+    int64_t* tdst = nullptr;        // [round's tasks] the band entry of each task
+    double* cost = nullptr;         // [k] best[0]
+    int* plen = nullptr;            // [k] nodes of the shortened path (0: no route)
+    int* err = nullptr;             // |= 1 chain deeper than stride, 4 steer overflow
+};
+// D and the pair count of every item, its chain into a.chain
+hipError_t launch_shortcut_chain(hipStream_t s, const ShortcutArgs& a);
+// one steer round: the pairs [g0, g0 + cnt), cnt <= the batch's round-B capacity — emit, prep,
+// walk, settle (the band entries).  ev (profiling, optional): 4 events, after each of the four.
+hipError_t launch_shortcut_round(hipStream_t s, const ShortcutArgs& a, int64_t g0, int cnt,
+                                 hipEvent_t* ev = nullptr);
+// the DP of every item over its band, then its path (a.chain compacted in place, plen, cost)
+hipError_t launch_shortcut_dp(hipStream_t s, const ShortcutArgs& a);
+// out[off[q] + e] = the e-th node of query q's shortened path (slot[q] its item or -1; off[Q] =
+// total, the device's copy of the host's scan of plen)
+hipError_t launch_shortcut_pack(hipStream_t s, const ShortcutArgs& a, int Q, const int* slot,
+                                const int64_t* off, int64_t total, int* out);
 
 // Revalidation (pp_rrt_revalidate / pp_batch_revalidate / pp_star_revalidate,
 // pp_k_revalidate.hip): re-verify every node's edge against the scene, propagate failures to the

@@ -1,5 +1,6 @@
 // pp_segments.cpp — planned paths as Dubins segments (pp_star_path_segments,
-// pp_batch_path_segments) and their sampling into trajectories (pp_segments_sample).  The chains,
+// pp_batch_path_segments; over caller-supplied chains: pp_star_chain_segments) and their sampling
+// into trajectories (pp_segments_sample).  The chains,
 // items, counts, scan and sizes-only protocol are the packed line exports' (pp_finish.cpp,
 // pp_star_goal.cpp); the kernels are pp_k_segments.hip.  DESIGN.md §3.7 "Segment export and
 // sampling".
@@ -199,6 +200,81 @@ int pp_star_path_segments(pp_ctx* ctx, const double* goals, const int32_t* nodes
     a.cnt = pe.cnt.p;
     a.okf = pe.ok.p;
     // the count pass: every item's edges (and whether its goal edge has a word)
+    if ((r = seg_launch(ctx, a, pe.items.p, k, true, false))) return r;
+    const SegPtrs out = seg_ptrs(seg);
+    bool go = false;
+    if ((r = seg_sizes(ctx, Q, off, seg != nullptr, cap, n_total, ok, &go)) || !go) return r;
+    return seg_write(ctx, a, pe.items.p, k, true, Q, off, out, length);
+}
+
+int pp_star_chain_segments(pp_ctx* ctx, const double* goals, const int64_t* coff,
+                           const int32_t* chain, int reverse, int64_t* off,
+                           const pp_path_segments* seg, int64_t cap, int64_t* n_total,
+                           double* length, uint8_t* ok) {
+    int r = check_ctx(ctx, true, false);
+    if (r) return r;
+    StarBatch& s = ctx->star;
+    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
+    if (!goals || !coff || !off || !n_total)
+        return set_err(PP_ERR_INVALID_ARGUMENT, "null goals, coff, off or n_total");
+    if (reverse != 0 && reverse != 1) return set_err(PP_ERR_INVALID_ARGUMENT, "reverse is 0 or 1");
+    const int Q = s.f.Q;
+    for (int q = 0; q < Q; ++q)
+        if (!finite3(goals + 3 * (size_t)q)) return set_err(PP_ERR_INVALID_ARGUMENT, "non-finite goal");
+    if (coff[0] != 0) return set_err(PP_ERR_INVALID_ARGUMENT, "coff[0] must be 0");
+    for (int q = 0; q < Q; ++q)
+        if (coff[q + 1] < coff[q]) return set_err(PP_ERR_INVALID_ARGUMENT, "coff must not decrease");
+    const int64_t nc = coff[Q];
+    if (nc > 0 && !chain) return set_err(PP_ERR_INVALID_ARGUMENT, "null chain");
+    hipStream_t st = ctx->stream;
+    // the chains against the trees as they are: every entry a node of its tree, the root last
+    std::vector<int> hn((size_t)Q);
+    PP_HIP(hipMemcpyAsync(hn.data(), s.f.n.p, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    std::vector<int32_t> nodes((size_t)Q, -1);
+    for (int q = 0; q < Q; ++q) {
+        const int64_t c0 = coff[q], c1 = coff[q + 1];
+        if (c1 == c0) continue;
+        if (c1 - c0 > kCfMaxDepth) return set_err(PP_ERR_INVALID_ARGUMENT, "a chain row longer than 8192 nodes");
+        for (int64_t e = c0; e < c1; ++e)
+            if (chain[e] < 0 || chain[e] >= hn[(size_t)q])
+                return set_err(PP_ERR_INVALID_ARGUMENT, "chain entry outside its query's tree");
+        if (chain[c1 - 1] != 0) return set_err(PP_ERR_INVALID_ARGUMENT, "a chain row must end in node 0 (the root)");
+        nodes[(size_t)q] = chain[c0];
+    }
+    PathExport& pe = ctx->paths;
+    int k = 0;
+    if ((r = paths_items(ctx, s.f, nodes.data(), &k))) return r;
+    seg_empty(Q, off, n_total, length, ok);
+    if (k == 0) return PP_OK;
+    Shortcut& sc = ctx->shortcut;
+    PP_HIP(sc.cchain.reserve((size_t)nc));
+    PP_HIP(sc.coff.reserve((size_t)Q + 1));
+    std::vector<int> items(1 + (size_t)k * kCfItem, 0);
+    items[0] = k;
+    for (int b = 0; b < k; ++b) items[1 + (size_t)b * kCfItem] = b;
+    PP_HIP(pe.items.reserve(items.size()));
+    PP_HIP(s.goal_d.reserve(3 * (size_t)Q));
+    PP_HIP(hipMemcpyAsync(sc.cchain.p, chain, (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemcpyAsync(sc.coff.p, coff, ((size_t)Q + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemcpyAsync(pe.items.p, items.data(), items.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemcpyAsync(s.goal_d.p, goals, 3 * (size_t)Q * sizeof(double), hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemsetAsync(pe.cnt.p, 0, (size_t)k * sizeof(int), st));
+    PP_HIP(hipMemsetAsync(pe.ok.p, 0, (size_t)k * sizeof(int), st));
+    PP_HIP(ctx->cf.err.reserve(2));
+    PP_HIP(hipMemsetAsync(ctx->cf.err.p, 0, 2 * sizeof(int), st));
+    SegArgs a;
+    a.tr = s.f.tree_dev();
+    a.row_cap = s.f.cap;
+    a.qidx = pe.qidx.p;
+    a.nodes = pe.nodes.p;
+    a.goals = s.goal_d.p;
+    a.turn_radius = ctx->scene.max_steer;
+    a.reverse = reverse;
+    a.cnt = pe.cnt.p;
+    a.okf = pe.ok.p;
+    a.cchain = sc.cchain.p;
+    a.coff = sc.coff.p;
     if ((r = seg_launch(ctx, a, pe.items.p, k, true, false))) return r;
     const SegPtrs out = seg_ptrs(seg);
     bool go = false;

@@ -1123,6 +1123,84 @@ class RRTStarBatch:
         off, seg, _, _ = self.path_segments(goals, nodes, reverse)
         return sample_segments(self.ctx, off, seg, ds)
 
+    # ---- shortcuts along the chain (pp_star_shortcut / _edges / pp_star_chain_segments, §3.7)
+    def _goals(self, goals):
+        g = np.asarray(goals, dtype=np.float64)
+        g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
+        return np.ascontiguousarray(g, dtype=np.float64).reshape(self.q, 3)
+
+    def shortcut(self, goals, nodes=None, span=8):
+        """Shorten every query's path goal -> node -> parent -> ... -> root by Dubins shortcuts
+        between the poses of its own chain (pp_star_shortcut): from each position an edge may skip
+        to any of the next ``span`` (1..63) positions when RRT*'s feasible edge between the two
+        stored poses verifies in the context's current scene, and a DP over the chain picks the
+        cheapest such route.  ``goals``, ``nodes`` as in ``paths`` (None: ``plan(goals)``'s best
+        nodes).  Returns (off int64[q + 1], chain int32[n], cost float64[q], ok bool[q]): row q =
+        ``chain[off[q]:off[q + 1]]``, the tree nodes after the goal, the root (0) last; empty
+        with cost inf and ``ok[q]`` False where the node is -1 or no route exists within the span.
+        ``n_tested``: the pairs considered.  ``span=1`` re-verifies the tree chain itself."""
+        g = self._goals(goals)
+        if nodes is None:
+            nodes = self.plan(g)[0]
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+        L = _ffi.lib()
+        ip, dp, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        u8 = C.POINTER(C.c_uint8)
+        off = np.zeros(self.q + 1, dtype=np.int64)
+        ok = np.zeros(self.q, dtype=np.uint8)
+        cost = np.zeros(self.q)
+        tot, tested = C.c_int64(0), C.c_int64(0)
+        # one call instead of sizes-then-fill (which would steer everything twice): a row is no
+        # longer than its tree, so the trees' total always suffices
+        cap = int(np.sum(self.state()[0], dtype=np.int64))
+        chain = np.zeros(max(cap, 1), dtype=np.int32)
+        _ffi.check(L.pp_star_shortcut(
+            self.ctx.handle, g.ctypes.data_as(dp), nodes.ctypes.data_as(ip), int(span),
+            off.ctypes.data_as(i64), chain.ctypes.data_as(ip), max(cap, 1), C.byref(tot),
+            cost.ctypes.data_as(dp), ok.ctypes.data_as(u8), C.byref(tested)))
+        self.n_tested = tested.value
+        return off, chain[:tot.value].copy(), cost, ok.astype(bool)
+
+    def shortcut_edges(self, query: int, goal, node: int, span: int):
+        """The band ``shortcut`` runs its DP over, for one query, un-culled (pp_star_shortcut_edges):
+        (cnode int32[D], w float64[D, span]) — ``cnode[i - 1]`` the tree node of chain position i
+        (position 0 is the goal), ``w[i, j - i - 1]`` the Dubins cost of the feasible edge from
+        position i to position j, inf where infeasible or j > D."""
+        g = np.ascontiguousarray(goal, dtype=np.float64).reshape(3)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        L = _ffi.lib()
+        d = C.c_int64(0)
+        _ffi.check(L.pp_star_shortcut_edges(self.ctx.handle, int(query), g.ctypes.data_as(dp),
+                                            int(node), int(span), None, None, 0, C.byref(d)))
+        D = d.value
+        w = np.zeros((D, int(span)))
+        cnode = np.zeros(D, dtype=np.int32)
+        _ffi.check(L.pp_star_shortcut_edges(self.ctx.handle, int(query), g.ctypes.data_as(dp),
+                                            int(node), int(span), w.ctypes.data_as(dp),
+                                            cnode.ctypes.data_as(ip), D, C.byref(d)))
+        return cnode, w
+
+    def chain_segments(self, goals, off, chain, reverse=False):
+        """``path_segments`` over caller-supplied chains (pp_star_chain_segments): row q = the
+        edges goal -> chain[off[q]] -> ... -> chain[off[q + 1] - 1] (``shortcut``'s rows, or any
+        chain of tree nodes ending in the root), nothing verified again.  Returns what
+        ``path_segments`` returns; an empty chain row gives an empty row with ``ok`` False."""
+        g = self._goals(goals)
+        coff = np.ascontiguousarray(off, dtype=np.int64).reshape(self.q + 1)
+        chain = np.ascontiguousarray(chain, dtype=np.int32)
+        L, h = _ffi.lib(), self.ctx.handle
+        ip, dp, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        return _path_segments(self.q, lambda *a: L.pp_star_chain_segments(
+            h, g.ctypes.data_as(dp), coff.ctypes.data_as(i64), chain.ctypes.data_as(ip),
+            int(bool(reverse)), *a))
+
+    def shortcut_trajectories(self, goals, ds, nodes=None, span=8, reverse=True):
+        """``shortcut(goals, nodes, span)``'s rows as segments (``chain_segments``) sampled every
+        ``ds`` (``sample_segments``): (poff, x, y, yaw, kappa, s), root to goal by default."""
+        coff, chain, _, _ = self.shortcut(goals, nodes, span)
+        off, seg, _, _ = self.chain_segments(goals, coff, chain, reverse)
+        return sample_segments(self.ctx, off, seg, ds)
+
     # ---- forest export / import (pp_star_forest_export / _import, DESIGN.md §3.9)
     def export_forest(self, queries=None):
         """The complete state of the slots ``queries`` (distinct, any order; None: all) in one
