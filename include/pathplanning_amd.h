@@ -53,7 +53,9 @@ extern "C" {
  *        pp_segments_sample added (planned paths as Dubins segments, sampled into
  *        trajectories), nothing else changed
  * 5 (+): pp_star_shortcut, pp_star_shortcut_edges and pp_star_chain_segments added (RRT* paths
- *        shortened by Dubins shortcuts along the chain), nothing else changed */
+ *        shortened by Dubins shortcuts along the chain), nothing else changed
+ * 5 (+): pp_star_shortcut_commit added (the chain's shortcuts written back into the RRT* trees as
+ *        rewires), nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -667,6 +669,37 @@ int pp_star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int
  * PP_ERR_INVALID_ARGUMENT for a query out of range or a NULL goal or depth. */
 int pp_star_shortcut_edges(pp_ctx* ctx, int query, const double goal[3], int32_t node, int span,
                            double* w, int32_t* cnode, int64_t cap, int64_t* depth);
+/* Commit the chain's shortcuts into the trees (CPU restatement: tests/star_shortcut_commit_ref.py):
+ * a shortcut edge (i -> j) is an RRT* rewire of chain node c_i onto its ancestor c_j, and this call
+ * performs those that pay.  goals, nodes (-1: skip), span, the positions and w(i, j) are
+ * pp_star_shortcut's; write m_i for the tree node of position i = 1 .. D (m_D the root).  Per
+ * query, on the device, in f64 with every sum one addition: c[D] = 0; for i = D - 1 down to 1, cur
+ * = c[i + 1] + edge_cost[m_i] (what m_i costs through its stored edge) and v = the first strict
+ * minimum in increasing j of c[j] + w(i, j), j = i + 1 .. min(i + span, D); when v < cur (strict,
+ * pp_star_extend's own rewire test) parent[m_i] = m_j, edge_cost[m_i] = w(i, j) and c[i] = v,
+ * else c[i] = cur and the node keeps its stored edge, whatever w(i, i + 1) says: the call neither
+ * verifies nor un-verifies a stored edge (like pp_star_extend on a tree that was not
+ * revalidated).  cost_out[q] = the first strict minimum over j = 1 .. min(span, D) of c[j] +
+ * w(0, j), node_out[q] = that m_j, n_rewired[q] = the chain nodes re-parented; -1, +inf and 0 when
+ * nodes[q] is -1 (the query is untouched) or no goal edge is feasible (the chain's rewires are
+ * committed all the same: the improvement is real).  Afterwards every node's cost is cost[parent]
+ * + edge_cost again, parents before children (the invariant pp_star_forest_import checks): c[i]
+ * on the chain, recomputed below it; a node without a changed ancestor keeps its cost bit for
+ * bit, and no cost rises.  The query's rewire counter (pp_star_state) advances by n_rewired[q];
+ * *n_changed = the nodes over the batch whose cost changed; *n_tested = pp_star_shortcut's pair
+ * count.  Poses, node order, tree sizes, iteration counters, seeds, focus, node_evals and stats
+ * are untouched, and later pp_star_extend calls continue from the committed trees exactly as from
+ * an imported copy of them.  When every w(i, i + 1) equals the stored edge cost (an unchanged
+ * scene), cost_out is pp_star_shortcut's cost and the tree chain from node_out is its row.
+ * Errors: everything pp_star_shortcut checks on the host, before any launch (NULL goals or nodes,
+ * span outside [1, 63], a non-finite goal, a node outside its tree: PP_ERR_INVALID_ARGUMENT;
+ * PP_ERR_STATE without an RRT* batch or a scene); a chain deeper than 8192 nodes or more than
+ * 2^26 pairs: PP_ERR_CAPACITY before any steer launch; PP_ERR_STEER_OVERFLOW leaves every tree
+ * unchanged bit for bit.  node_out, cost_out, n_rewired (q entries each), n_tested and n_changed
+ * may be NULL. */
+int pp_star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes, int span,
+                            int32_t* node_out, double* cost_out, int32_t* n_rewired,
+                            int64_t* n_tested, int64_t* n_changed);
 /* pp_star_path_segments over caller-supplied chains: row i = goal -> chain[coff[i]] -> ... ->
  * chain[coff[i + 1] - 1] on query i's tree (coff: q + 1 entries, coff[0] = 0, not decreasing) —
  * pp_star_shortcut's rows, or any chain of tree nodes that ends in the root.  The words, the three

@@ -14,7 +14,7 @@
 //   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
 //   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_star_chain_segments,
 //                    pp_segments_sample
-//   pp_shortcut.cpp  pp_star_shortcut, pp_star_shortcut_edges
+//   pp_shortcut.cpp  pp_star_shortcut, pp_star_shortcut_edges, pp_star_shortcut_commit
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -470,7 +470,7 @@ struct ForestIo {
 // ---- shortcuts along the chain (pp_star_shortcut / pp_star_shortcut_edges: ShortcutArgs), sized
 // to the call; cchain / coff: pp_star_chain_segments' uploaded chains
 struct Shortcut {
-    DBuf<int> chain, next, depth, plen, err, out, cchain;
+    DBuf<int> chain, next, depth, plen, err, out, cchain, res;
     DBuf<int64_t> npair, pbase, boff, tdst, off, coff;
     DBuf<double> band, cost;
 };

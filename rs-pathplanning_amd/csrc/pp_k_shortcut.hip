@@ -24,6 +24,10 @@
 //   shortcut_pack    the rows into the packed CSR output
 // Nothing of the trees or the extend's own state is written: round B's arrays, the records and
 // stB->W are rewritten by every extend step before it reads them (as the goal rounds).
+// pp_star_shortcut_commit runs the same chain and rounds and then, instead of the DP and the pack,
+//   shortcut_commit  one wave per item: the DP anchored at the tree's stored edges, its rewires
+//                    written into the tree, and the costs of the subtrees below recomputed
+// (the only kernel of this unit that writes trees: parent, elen, cost, mark, stamp, rewires).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -249,6 +253,158 @@ __global__ __launch_bounds__(256) void shortcut_pack_kernel(ShortcutArgs a, int 
     const int64_t r = e - off[lo];
     if (b < 0 || r >= a.plen[b]) return;
     out[e] = a.chain[(size_t)b * a.stride + (size_t)r];
+}
+
+// pp_star_shortcut_commit (DESIGN.md §3.7 "Committing shortcuts"; restated on the CPU in
+// tests/star_shortcut_commit_ref.py): instead of shortcut_dp / shortcut_pack, the DP anchored at
+// the tree and written back into it.  One wave per item, the wave that alone touches its query's
+// rows.  c[D] = 0; for i = D - 1 .. 1 with m = the tree node of position i: cur = c[i + 1] +
+// elen[m] (what propagation alone would give m), v = the first strict minimum in increasing j of
+// c[j] + w(i, j); v < cur (strict, star_rewire's test) re-parents m onto position j's node with
+// edge cost w(i, j) and c[i] = v, else c[i] = cur and the stored edge stays, whatever w(i, i + 1)
+// says.  c[] lives in shortcut_dp's lane ring.  Lane 0 writes the rewired nodes' parent / elen and
+// every changed c[i] with the query's level stamp; then the subtrees under the stamped nodes are
+// recomputed level by level exactly as star_rewire_kernel does after one rewire, here once for
+// the whole chain: a chain node that is recomputed gets cost[parent] + elen = c[i] again, bit for
+// bit, and a node is only ever recomputed from a parent that is already final, so every store is
+// the node's final cost and the first one alone can differ from the old cost (the count).
+// A steer error of the rounds (a.err) leaves everything unwritten.
+// res[3 b ..] = the goal's node (-1: no feasible goal edge), the rewires reported (0 then), the
+// costs changed; a.cost[b] = the goal's cost or +inf.
+__global__ __launch_bounds__(64 * kScWaves) void shortcut_commit_kernel(ShortcutArgs a) {
+    const int lane = __lane_id();
+    const int b = (int)blockIdx.x * kScWaves + (int)(threadIdx.x >> 6);
+    if (b >= a.k) return;
+    const int D = a.depth[b];
+    if (D <= 0 || a.err[0] != 0) {
+        if (lane == 0) {
+            a.cost[b] = __builtin_inf();
+            a.res[3 * b] = -1;
+            a.res[3 * b + 1] = 0;
+            a.res[3 * b + 2] = 0;
+        }
+        return;
+    }
+    const StarDev& sd = a.a.sd;
+    const MqDev& mq = sd.mq;
+    const int q = a.qidx[b];
+    const size_t row = (size_t)q * mq.cap;
+    double* __restrict__ cost = sd.cost + row;
+    double* __restrict__ elen = sd.elen + row;
+    int* __restrict__ par = mq.parent + row;
+    int* __restrict__ mark = sd.mark + row;
+    const int* __restrict__ ch = a.chain + (size_t)b * a.stride;
+    const int sp = min(a.span, D);
+    const double* __restrict__ W = a.band + a.boff[b];
+    int s = sd.stamp[q];
+    double ring = lane == (D & 63) ? 0.0 : __builtin_inf();
+    int nrw = 0, nchg = 0;  // (lane 0's count of changed chain costs; nrw is wave-uniform)
+    for (int i0 = D - 1; i0 >= 1; i0 -= kScPrefetch) {
+        double w[kScPrefetch];
+#pragma unroll
+        for (int r = 0; r < kScPrefetch; ++r) {  // the rows' loads, ahead of their serial steps
+            const int i = i0 - r;
+            const bool has = i >= 1 && lane < sp && i + 1 + lane <= D;
+            w[r] = has ? W[(size_t)i * sp + lane] : __builtin_inf();
+        }
+        // lane r: row i0 - r's tree node, its stored edge cost and cost (the rows' nodes are
+        // distinct, so no store of an earlier row aliases these)
+        int mn = 0;
+        double me = 0.0, mc = 0.0;
+        if (lane < kScPrefetch && i0 - lane >= 1) {
+            mn = ch[i0 - lane - 1];
+            me = elen[mn];
+            mc = cost[mn];
+        }
+#pragma unroll
+        for (int r = 0; r < kScPrefetch; ++r) {
+            const int i = i0 - r;
+            if (i < 1) break;
+            const int m = __shfl(mn, r);
+            const double cur = __shfl(ring, (i + 1) & 63) + __shfl(me, r);
+            const double old = __shfl(mc, r);
+            const double bj = __shfl(ring, (i + 1 + lane) & 63);
+            double v = w[r] <= 1.7976931348623157e308 ? bj + w[r] : __builtin_inf();
+            if (!(v <= 1.7976931348623157e308)) v = __builtin_inf();
+            int bl = lane;
+            wave_argmin(v, bl);  // the lowest lane (the lowest j) on an exact tie
+            const double wj = __shfl(w[r], bl);
+            const bool rw = v < cur;
+            const double ci = rw ? v : cur;
+            if (lane == (i & 63)) ring = ci;
+            if (lane == 0) {
+                if (rw) {
+                    par[m] = ch[i + bl];  // position j = i + 1 + bl
+                    elen[m] = wj;
+                }
+                if (ci != old) {
+                    cost[m] = ci;
+                    mark[m] = s;
+                    ++nchg;
+                }
+            }
+            nrw += rw ? 1 : 0;
+        }
+    }
+    // the goal: position 0 over c[1 .. sp]
+    const double bj0 = __shfl(ring, (1 + lane) & 63);
+    const double w0 = lane < sp ? W[lane] : __builtin_inf();
+    double v0 = w0 <= 1.7976931348623157e308 ? bj0 + w0 : __builtin_inf();
+    if (!(v0 <= 1.7976931348623157e308)) v0 = __builtin_inf();
+    int bl0 = lane;
+    wave_argmin(v0, bl0);
+    const bool reach = v0 <= 1.7976931348623157e308;
+    // the subtrees under the changed chain nodes, level by level (star_rewire_kernel's pass): this
+    // wave alone reads and writes query q's rows, so workgroup-scope fences order its lanes
+    int cnt = 0;
+    if (__shfl(nchg, 0) > 0) {
+        const int n = mq.n[q];
+        __threadfence_block();
+        for (;;) {
+            bool any = false;
+            for (int j0 = 0; j0 < n; j0 += 64 * kRwReg) {
+                int pr[kRwReg], mk[kRwReg];
+#pragma unroll
+                for (int r = 0; r < kRwReg; ++r) {
+                    const int j = j0 + lane + 64 * r;
+                    pr[r] = j < n ? par[j] : -1;
+                }
+#pragma unroll
+                for (int r = 0; r < kRwReg; ++r) mk[r] = pr[r] >= 0 ? mark[pr[r]] : 0;
+#pragma unroll
+                for (int r = 0; r < kRwReg; ++r) {
+                    if (pr[r] >= 0 && mk[r] == s) {
+                        const int j = j0 + lane + 64 * r;
+                        const double c = cost[pr[r]] + elen[j];
+                        if (c != cost[j]) ++cnt;
+                        cost[j] = c;
+                        mark[j] = s + 1;
+                        any = true;
+                    }
+                }
+            }
+            __threadfence_block();
+            ++s;
+            if (!__ballot(any)) break;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) {
+        const int rep = reach ? nrw : 0;
+        sd.stamp[q] = s;
+        sd.rewires[q] += rep;
+        a.cost[b] = reach ? v0 : __builtin_inf();
+        a.res[3 * b] = reach ? ch[bl0] : -1;
+        a.res[3 * b + 1] = rep;
+        a.res[3 * b + 2] = nchg + cnt;
+    }
+}
+
+hipError_t launch_shortcut_commit(hipStream_t s, const ShortcutArgs& a) {
+    if (a.k <= 0 || !a.res) return hipErrorInvalidValue;
+    shortcut_commit_kernel<<<(a.k + kScWaves - 1) / kScWaves, 64 * kScWaves, 0, s>>>(a);
+    return hipGetLastError();
 }
 
 hipError_t launch_shortcut_chain(hipStream_t s, const ShortcutArgs& a) {

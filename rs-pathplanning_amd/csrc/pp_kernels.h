@@ -388,6 +388,8 @@ struct ShortcutArgs {
     double* cost = nullptr;         // [k] best[0]
     int* plen = nullptr;            // [k] nodes of the shortened path (0: no route)
     int* err = nullptr;             // |= 1 chain deeper than stride, 4 steer overflow
+    int* res = nullptr;             // [3 * k] pp_star_shortcut_commit: the goal's node (-1 none), the
+                                    // rewires reported, the costs changed (cost: the goal's cost)
 };
 // D and the pair count of every item, its chain into a.chain
 hipError_t launch_shortcut_chain(hipStream_t s, const ShortcutArgs& a);
@@ -397,6 +399,11 @@ hipError_t launch_shortcut_round(hipStream_t s, const ShortcutArgs& a, int64_t g
                                  hipEvent_t* ev = nullptr);
 // the DP of every item over its band, then its path (a.chain compacted in place, plen, cost)
 hipError_t launch_shortcut_dp(hipStream_t s, const ShortcutArgs& a);
+// pp_star_shortcut_commit, after the rounds in place of the DP: the tree-anchored DP of every item,
+// its rewires written into the tree (parent, elen, cost), the subtrees' costs recomputed (mark /
+// stamp as star_rewire leaves them), rewires[q] advanced; a.res and a.cost.  Writes nothing when
+// *a.err is set by the rounds.
+hipError_t launch_shortcut_commit(hipStream_t s, const ShortcutArgs& a);
 // out[off[q] + e] = the e-th node of query q's shortened path (slot[q] its item or -1; off[Q] =
 // total, the device's copy of the host's scan of plen)
 hipError_t launch_shortcut_pack(hipStream_t s, const ShortcutArgs& a, int Q, const int* slot,

@@ -2505,7 +2505,6 @@ __global__ __launch_bounds__(256) void star_insert_kernel(
     }
 }
 
-constexpr int kRwReg = 16;  // rewire propagation: node rows per lane and batch of gathers
 __global__ __launch_bounds__(256) void star_rewire_kernel(
     StarDev sd, SceneDev sc, const SteerTask* __restrict__ tasksC,
     const StarTaskExt* __restrict__ extC, const int* __restrict__ statusC,

@@ -1,6 +1,7 @@
 // pp_shortcut.cpp — shorten the RRT* batch's paths by Dubins shortcuts along the chain:
-// pp_star_shortcut (every query's shortened chain in one call) and pp_star_shortcut_edges (the
-// un-culled band of one query, the test hook).  The kernels are pp_k_shortcut.hip; the items and
+// pp_star_shortcut (every query's shortened chain in one call), pp_star_shortcut_edges (the
+// un-culled band of one query, the test hook) and pp_star_shortcut_commit (the shortcuts written
+// back into the trees as rewires).  The kernels are pp_k_shortcut.hip; the items and
 // the sizes-only protocol are the packed exports' (pp_finish.cpp, pp_star_goal.cpp).  DESIGN.md
 // §3.7 "Shortcuts along the chain".
 #include <limits>
@@ -238,9 +239,113 @@ int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int sp
     return rc;
 }
 
+// pp_star_shortcut_commit.  ms (profiling, may be null): [0] chain + sizes, [1] the steer rounds,
+// [2] the commit kernel (DP, writes, propagation), [3] the copies back
+int star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes, int span,
+                         int32_t* node_out, double* cost_out, int32_t* n_rewired,
+                         int64_t* n_tested, int64_t* n_changed, double* ms) {
+    int r = star_ready(ctx);
+    if (r) return r;
+    if (span < 1 || span > kStarKMax) return set_err(PP_ERR_INVALID_ARGUMENT, "span outside [1, 63]");
+    if (!goals || !nodes) return set_err(PP_ERR_INVALID_ARGUMENT, "null goals or nodes");
+    StarBatch& s = ctx->star;
+    Shortcut& sc = ctx->shortcut;
+    const int Q = s.f.Q;
+    for (int q = 0; q < Q; ++q)
+        if (!finite3(goals + 3 * (size_t)q)) return set_err(PP_ERR_INVALID_ARGUMENT, "non-finite goal");
+    hipStream_t st = ctx->stream;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    auto drop = [&]() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    };
+    if (ms) {
+        for (hipEvent_t& e : ev) PP_HIP(hipEventCreate(&e));
+        PP_HIP(hipEventRecord(ev[0], st));
+    }
+    ScRun run;
+    if ((r = shortcut_sizes(ctx, goals, nodes, span, run))) {
+        drop();
+        return r;
+    }
+    const int k = run.k;
+    if (node_out) std::fill(node_out, node_out + Q, (int32_t)-1);
+    if (cost_out) std::fill(cost_out, cost_out + Q, std::numeric_limits<double>::infinity());
+    if (n_rewired) std::fill(n_rewired, n_rewired + Q, (int32_t)0);
+    if (n_tested) *n_tested = k ? run.pbase[(size_t)k] : 0;
+    if (n_changed) *n_changed = 0;
+    if (ms) std::fill(ms, ms + 4, 0.0);
+    if (k == 0) {
+        drop();
+        return PP_OK;
+    }
+    if (ms) PP_HIP(hipEventRecord(ev[1], st));
+    if ((r = shortcut_rounds(ctx, run))) {
+        drop();
+        return r;
+    }
+    if (ms) PP_HIP(hipEventRecord(ev[2], st));
+    PP_HIP(sc.res.reserve(3 * (size_t)k));
+    run.a.res = sc.res.p;
+    // (the kernel reads the rounds' error word itself and writes nothing when it is set: no host
+    // round trip between the rounds and the tree's stores)
+    PP_HIP(launch_shortcut_commit(st, run.a));
+    if (ms) PP_HIP(hipEventRecord(ev[3], st));
+    std::vector<int> res(3 * (size_t)k);
+    std::vector<double> hc((size_t)k);
+    int err = 0;
+    PP_HIP(hipMemcpyAsync(res.data(), sc.res.p, res.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(hc.data(), sc.cost.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(&err, sc.err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (ms) PP_HIP(hipEventRecord(ev[4], st));
+    PP_HIP(hipStreamSynchronize(st));
+    if ((r = shortcut_error(err))) {
+        drop();
+        return r;
+    }
+    int64_t changed = 0;
+    for (int q = 0; q < Q; ++q) {
+        const int b = run.slot[(size_t)q];
+        if (b < 0) continue;
+        if (node_out) node_out[q] = res[3 * (size_t)b];
+        if (cost_out) cost_out[q] = hc[(size_t)b];
+        if (n_rewired) n_rewired[q] = res[3 * (size_t)b + 1];
+        changed += res[3 * (size_t)b + 2];
+    }
+    if (n_changed) *n_changed = changed;
+    if (ms) {
+        float f = 0.0f;
+        for (int i = 0; i < 4; ++i) {
+            PP_HIP(hipEventElapsedTime(&f, ev[i], ev[i + 1]));
+            ms[i] = f;
+        }
+    }
+    drop();
+    return PP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pp_star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes, int span,
+                            int32_t* node_out, double* cost_out, int32_t* n_rewired,
+                            int64_t* n_tested, int64_t* n_changed) {
+    return star_shortcut_commit(ctx, goals, nodes, span, node_out, cost_out, n_rewired, n_tested,
+                                n_changed, nullptr);
+}
+
+// pp_star_shortcut_commit with its stages timed by events (ms: 4 values — chain + sizes, the steer
+// rounds, the commit kernel, the copies back): measurement only
+// (scripts/bench_star_shortcut_commit.py), not declared in the header and not part of the ABI
+int ppamd_star_shortcut_commit_debug(pp_ctx* ctx, const double* goals, const int32_t* nodes,
+                                     int span, int32_t* node_out, double* cost_out,
+                                     int32_t* n_rewired, int64_t* n_tested, int64_t* n_changed,
+                                     double* ms) {
+    return star_shortcut_commit(ctx, goals, nodes, span, node_out, cost_out, n_rewired, n_tested,
+                                n_changed, ms);
+}
+
 
 int pp_star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int span,
                      int64_t* off, int32_t* chain, int64_t cap, int64_t* n_total, double* cost,

@@ -247,6 +247,7 @@ struct MqDev {
 // (X_near), C: the rewire edges X_near → new — each an explicit-task steer_prep / steer_walk pass
 // whose task count the previous kernel sets on the device.
 constexpr int kStarKMax = 63;  // neighbours per insert: with the nearest, <= 64 candidates (lanes)
+constexpr int kRwReg = 16;  // rewire propagation: node rows per lane and batch of gathers
 constexpr int kStarFocusDraws = 1024;  // PP_STAR_FOCUS_DRAWS: draws an iteration tries (16 wave rounds)
 struct StarDev {
     MqDev mq;            // trees, iteration counters, seeds, blocked roots, targets (K = 1)

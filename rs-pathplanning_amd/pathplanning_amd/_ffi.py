@@ -52,6 +52,7 @@ EXPORTED = [
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_star_path_segments", "pp_batch_path_segments", "pp_segments_sample",
     "pp_star_shortcut", "pp_star_shortcut_edges", "pp_star_chain_segments",
+    "pp_star_shortcut_commit",
     "pp_star_forest_export", "pp_star_forest_import", "pp_batch_forest_export",
     "pp_batch_forest_import",
     "pp_rrt_get_stats", "pp_rrt_reset_stats", "pp_set_profiling",
@@ -242,6 +243,7 @@ def lib():
                                         i64p], C.c_int),
             "pp_star_chain_segments": ([vp, dp, i64p, ip, C.c_int, i64p, C.POINTER(PathSegmentsC),
                                         C.c_int64, i64p, dp, C.POINTER(C.c_uint8)], C.c_int),
+            "pp_star_shortcut_commit": ([vp, dp, ip, C.c_int, ip, dp, ip, i64p, i64p], C.c_int),
             "pp_star_forest_export": ([vp, ip, C.c_int, C.POINTER(ForestStateC), C.c_int64, i64p],
                                       C.c_int),
             "pp_star_forest_import": ([vp, ip, C.c_int, C.POINTER(ForestStateC), ip], C.c_int),

@@ -999,25 +999,30 @@ class RRTStarBatch:
         return n, new_index[:total]
 
     # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path)
-    def plan(self, goals, focus: bool = False, prune: bool = False):
+    def plan(self, goals, focus: bool = False, prune: bool = False, commit=None):
         """The cheapest feasible goal edge of every query on its tree as extended so far: goal
         (gx, gy, gyaw) per query (one pose is broadcast to all).  Returns (best_node int32[q],
         cost float64[q]): -1 and inf where no node reaches the goal.  ``n_checked``: the
         (query, node) pairs considered.  ``focus``: then ``focus(goals, cost)`` on the result.
         ``prune`` (needs ``focus``): then ``prune(keep=best_node)``; the best nodes returned are
-        their indices in the pruned trees."""
+        their indices in the pruned trees.  ``commit`` (a span, 1..63): after the plan,
+        ``shortcut_commit(goals, best_node, commit)``; the node and cost returned are the
+        commit's, and ``focus`` / ``prune`` use them."""
         if prune and not focus:
             raise ValueError("plan(prune=True) needs focus=True: the prune reads the focus")
+        if commit is not None:
+            node, cost = self.plan(goals)
+            node, cost, _ = self.shortcut_commit(goals, node, int(commit))
+            if focus:
+                self.focus(goals, cost)
+            if prune:
+                node = self._prune_keep(node)
+            return node, cost
         if focus:
             node, cost = self.plan(goals)
             self.focus(goals, cost)
             if prune:
-                n_old = self.state()[0]
-                _, new_index = self.prune(keep=node, n_old=n_old)
-                off = np.concatenate(([0], np.cumsum(n_old[:-1], dtype=np.int64)))
-                has = node >= 0
-                node = node.copy()
-                node[has] = new_index[off[has] + node[has]]
+                node = self._prune_keep(node)
             return node, cost
         g = np.asarray(goals, dtype=np.float64)
         g = np.tile(g, (self.q, 1)) if g.ndim == 1 else g
@@ -1031,6 +1036,16 @@ class RRTStarBatch:
             cost.ctypes.data_as(dp), C.byref(chk)))
         self.n_checked = chk.value
         return node, cost
+
+    def _prune_keep(self, node):
+        """``prune(keep=node)``; the nodes' indices in the pruned trees"""
+        n_old = self.state()[0]
+        _, new_index = self.prune(keep=node, n_old=n_old)
+        off = np.concatenate(([0], np.cumsum(n_old[:-1], dtype=np.int64)))
+        has = node >= 0
+        node = node.copy()
+        node[has] = new_index[off[has] + node[has]]
+        return node
 
     def goal_costs(self, query: int, goal):
         """total[m] = cost[m] + the goal edge's Dubins cost of every node of one query (inf where
@@ -1160,6 +1175,35 @@ class RRTStarBatch:
             cost.ctypes.data_as(dp), ok.ctypes.data_as(u8), C.byref(tested)))
         self.n_tested = tested.value
         return off, chain[:tot.value].copy(), cost, ok.astype(bool)
+
+    def shortcut_commit(self, goals, nodes=None, span=8):
+        """Write ``shortcut``'s improvements back into the trees (pp_star_shortcut_commit): along
+        every query's chain goal -> node -> parent -> ... -> root, from the root's end, a chain
+        node is re-parented onto the ancestor at most ``span`` (1..63) positions up the chain whose
+        feasible edge gives it a strictly cheaper cost than its stored edge does (RRT*'s rewire
+        test); the costs of everything below are recomputed, so ``plan``, ``paths``,
+        ``path_segments``, ``focus``, ``prune`` and ``extend`` see the shorter route.  Poses, node
+        order and tree sizes stay; no cost rises.  ``goals``, ``nodes`` as in ``shortcut``.
+        Returns (node int32[q], cost float64[q], n_rewired int32[q]): the chain node the goal
+        connects to most cheaply within the span and that cost (-1, inf and 0 where the node is -1
+        or no goal edge is feasible).  ``n_tested``: the pairs considered; ``n_changed``: the
+        nodes whose cost changed."""
+        g = self._goals(goals)
+        if nodes is None:
+            nodes = self.plan(g)[0]
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        node = np.zeros(self.q, dtype=np.int32)
+        cost = np.zeros(self.q)
+        nrw = np.zeros(self.q, dtype=np.int32)
+        tested, changed = C.c_int64(0), C.c_int64(0)
+        _ffi.check(_ffi.lib().pp_star_shortcut_commit(
+            self.ctx.handle, g.ctypes.data_as(dp), nodes.ctypes.data_as(ip), int(span),
+            node.ctypes.data_as(ip), cost.ctypes.data_as(dp), nrw.ctypes.data_as(ip),
+            C.byref(tested), C.byref(changed)))
+        self.n_tested = tested.value
+        self.n_changed = changed.value
+        return node, cost, nrw
 
     def shortcut_edges(self, query: int, goal, node: int, span: int):
         """The band ``shortcut`` runs its DP over, for one query, un-culled (pp_star_shortcut_edges):
