@@ -1,6 +1,6 @@
 // pp_chain_dev.h — the chains of poses whose consecutive pairs are a planned path's Dubins edges,
-// shared by the line kernels (pp_kernels.hip: check_finish, cf_line_kernel, paths_kernel) and the
-// segment export (pp_k_segments.hip): a pose, a node's ancestor path, and the two pose providers.
+// shared by the line kernels (pp_k_finish.hip: check_finish, cf_line_kernel, paths_kernel) and
+// the segment export (pp_k_segments.hip): a pose, a node's ancestor path, and the two pose providers.
 #pragma once
 
 #include <hip/hip_runtime.h>

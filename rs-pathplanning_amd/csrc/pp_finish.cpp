@@ -155,7 +155,7 @@ int cf_run(pp_ctx* c, const TreeDev& tr, const int* nodes, int k, int want_line,
     return cf_error(err & ~32);
 }
 
-// pp_batch_plan's check_finish in steer rounds (CfbArgs, pp_kernels.hip): phase A rounds fill
+// pp_batch_plan's check_finish in steer rounds (CfbArgs, pp_k_finish.hip): phase A rounds fill
 // ftab for every node, phase B the goal and copy edges, the assemble kernel decides every item
 // whose verdicts are known, and check_finish_kernel runs the rest (literal paths, errors) with
 // the memo filled.  The same results as cf_run over all items; polygon scenes and batches with

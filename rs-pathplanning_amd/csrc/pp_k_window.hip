@@ -15,7 +15,8 @@
 //   steer_prep     8 lanes per (sample, parent): compute_yaw + Dubins word + grid-point distances
 //   steer_walk     one wave per task: sampled-arc polyline, bounds + disc collision, f64
 //                                                               rrt.rs:169-175,414-426, dubins.rs
-// check_finish, the query batch and the RRT* batch with its goal connection are pp_kernels.hip.
+// check_finish, the query batch and the RRT* batch with its goal connection are pp_k_finish.hip,
+// pp_k_batch.hip and pp_k_star.hip.
 // steer_prep, steer_walk and the API kernels (steer_tasks, verify_lines, dubins_*) are compiled by
 // pp_k_steer.hip alone and launched through pp_steer_launch.h; the device code the units inline
 // is pp_steer_dev.h.

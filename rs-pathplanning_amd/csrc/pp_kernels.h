@@ -1,5 +1,5 @@
 // pp_kernels.h — host-side launch wrappers of the HIP kernels, the one header of them that the
-// host side includes.  A section that names no unit is implemented in pp_kernels.hip.
+// host side includes.  Every section names the unit that implements it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -85,7 +85,7 @@ hipError_t launch_steer_tasks(hipStream_t st, const SceneDev& sc, const TreeDev&
                               const SteerTask* tasks, int n, int* out_status, double* out_yaw,
                               double* scratch);
 
-// check_finish, the packed line export and the batch plan's rounds (pp_kernels.hip).
+// check_finish, the packed line export and the batch plan's rounds (pp_k_finish.hip).
 // RRT::check_finish for k tree nodes (one wave per node, at most `grid` workgroups of kCfWaves
 // waves; gpath: grid * kCfWaves * kCfMaxDepth ints, the waves' ancestor paths).  ok/len/npts per
 // node; chain (optional) = k rows of [levels, edges, optimize's chosen ancestors...] with
@@ -116,7 +116,7 @@ struct CfBatch {
     const int* moff = nullptr;
 };
 
-// check_finish of a query batch in steer rounds (pp_batch_plan, see pp_kernels.hip): phase A
+// check_finish of a query batch in steer rounds (pp_batch_plan, see pp_k_finish.hip): phase A
 // fills ftab for every node, phase B the goal edges (gotab) and copy edges (gtab), the assemble
 // kernel decides every item whose verdicts are all known and lists the others (plist, pcount)
 // for check_finish_kernel.  Node b < nitems is item b, b - nitems < Q query's root.
@@ -198,7 +198,8 @@ hipError_t launch_check_finish(hipStream_t st, const SceneDev& sc, const SceneDe
 constexpr int kCfWaves = 4;                     // check_finish: waves (nodes in flight) per workgroup
 constexpr int kCfItem = 4 + kCfLevels;          // a line item: b, s, verified, 0, pos[kCfLevels]
 
-// Packed line export (pp_batch_paths / pp_star_paths): the lines of the line items (the layout
+// Packed line export (pp_batch_paths / pp_star_paths, pp_k_finish.hip): the lines of the line
+// items (the layout
 // above; item b = node nodes[b] of query qidx[b] of a forest) into one CSR buffer, every row root
 // side first.  star = false: finalize's chain of a check_finish item (s, pos[] from the item;
 // always the write pass — check_finish's own line pass counted); star = true: pp_star_path's chain
@@ -264,8 +265,8 @@ struct SegArgs {
 };
 hipError_t launch_segments(hipStream_t st, const SegArgs& a, int grid, int* err, const int* items,
                            int items_cap, bool star, bool write);
-// The sampler (pp_segments_sample).  Prefix: per row r = segments [off[r], off[r + 1]) the
-// running arc position P[j] = len[off[r]] + ... + len[j] added in row order, the row's length
+// The sampler (pp_segments_sample, pp_k_segments.hip).  Prefix: per row r = segments
+// [off[r], off[r + 1]) the running arc position P[j] = len[off[r]] + ... + len[j] added in row order, the row's length
 // rowlen[r], nfull[r] = floor(rowlen / ds) (clamped to max_samples) and its sample count cnt[r]
 // (nfull + 1, one more when rowlen > nfull * ds; 0 for a row without segments).  Sample: output i
 // of row r (poff[r] <= i < poff[r + 1]) at s = k ds (k = i - poff[r] <= nfull[r]) or rowlen[r],
@@ -295,14 +296,16 @@ struct SegSampleArgs {
 hipError_t launch_segments_prefix(hipStream_t st, const SegSampleArgs& a);
 hipError_t launch_segments_sample(hipStream_t st, const SegSampleArgs& a);
 
-// pp_batch_plan: the (query, node) items of the accepted nodes (off: [Q + 1] exclusive scan of
-// n_q - 1), and per query the first minimum length over its items' check_finish results
+// pp_batch_plan (pp_k_finish.hip): the (query, node) items of the accepted nodes (off: [Q + 1]
+// exclusive scan of n_q - 1), and per query the first minimum length over its items'
+// check_finish results
 hipError_t launch_mq_plan_items(hipStream_t s, int Q, const int* off, int* qidx, int* nodes);
 hipError_t launch_mq_plan_reduce(hipStream_t s, int Q, const int* off, const int* ok,
                                  const double* len, const int* npts, int* best_node,
                                  double* best_len, int* best_npts, int* n_fin);
 
-// Multi-query batch: `steps` lockstep extend iterations of every query (config 3).
+// Multi-query batch (pp_k_batch.hip): `steps` lockstep extend iterations of every query
+// (config 3).
 struct MqArgs {
     MqDev mq{};
     SceneDev sc{};
@@ -324,8 +327,8 @@ hipError_t launch_mq_init(hipStream_t s, const MqDev& mq, const double* starts);
 // the per-query iteration targets of a pp_batch_extend(n_steps) call
 hipError_t launch_mq_target(hipStream_t s, const MqDev& mq, int64_t n_steps, int64_t* target);
 
-// RRT* query batch (config 5): `steps` lockstep RRT* iterations of every query.  Task arrays of
-// round A hold Q entries, rounds B and C Q * kStarKMax; rec is shared by the rounds.
+// RRT* query batch (config 5, pp_k_star.hip): `steps` lockstep RRT* iterations of every query.
+// Task arrays of round A hold Q entries, rounds B and C Q * kStarKMax; rec is shared by the rounds.
 struct StarArgs {
     StarDev sd{};
     SceneDev sc{};
@@ -343,8 +346,8 @@ struct StarArgs {
 hipError_t launch_star_steps(hipStream_t s, const StarArgs& a, int steps);
 hipError_t launch_star_init(hipStream_t s, const StarArgs& a, const double* starts);
 
-// RRT* goal connection (pp_star_plan / pp_star_goal_costs): `rounds` rounds of 63 nodes per query
-// over the queries [q0, q1) of the batch `a` views, which lends round B's task arrays, the records
+// RRT* goal connection (pp_star_plan / pp_star_goal_costs, pp_k_star.hip): `rounds` rounds of 63
+// nodes per query over the queries [q0, q1) of the batch `a` views, which lends round B's task arrays, the records
 // and stB->W.  Per query: best (+inf none) and best_node (-1 none), the first strict minimum of
 // cost(m) + the goal edge's Dubins cost over the feasible nodes.
 struct StarGoalArgs {

@@ -1,4 +1,4 @@
-"""The RRT* kNN selection of star_knn (pp_kernels.hip) restated with numpy lanes and checked
+"""The RRT* kNN selection of star_knn (pp_k_star.hip) restated with numpy lanes and checked
 against a plain sort: node i sits in lane i % 64; T = the k-th smallest lane minimum; every node
 with d2 <= T is a candidate; the candidates sorted by (d2, index) start with the exact k nearest.
 When there are more than 64 candidates the kernel falls back to k exclusion rounds, restated here

@@ -56,3 +56,15 @@ def test_shortcut_unit_is_built(built):
     assert "pp_k_shortcut.hip" in built.SOURCES and "pp_shortcut.cpp" in built.SOURCES
     for f in ("pp_k_shortcut.hip", "pp_shortcut.cpp"):
         assert os.path.exists(os.path.join(built.CSRC, f))
+
+
+def test_every_source_file_is_listed(built):
+    """csrc/ and the build's lists name the same files, in both directions: a file missing from
+    SOURCES is not compiled, one missing from HEADERS does not make the library stale"""
+    files = os.listdir(built.CSRC)
+    assert len(set(built.SOURCES)) == len(built.SOURCES)
+    assert len(set(built.HEADERS)) == len(built.HEADERS)
+    assert sorted(built.SOURCES) == sorted(f for f in files if f.endswith((".hip", ".cpp")))
+    assert sorted(built.HEADERS) == sorted(f for f in files if f.endswith(".h"))
+    # the kernel split is complete: every kernel unit is named after its subsystem
+    assert "pp_kernels.hip" not in files
