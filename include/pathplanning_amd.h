@@ -55,7 +55,9 @@ extern "C" {
  * 5 (+): pp_star_shortcut, pp_star_shortcut_edges and pp_star_chain_segments added (RRT* paths
  *        shortened by Dubins shortcuts along the chain), nothing else changed
  * 5 (+): pp_star_shortcut_commit added (the chain's shortcuts written back into the RRT* trees as
- *        rewires), nothing else changed */
+ *        rewires), nothing else changed
+ * 5 (+): pp_star_advance added (a node of every RRT* tree becomes its root; what hung from its
+ *        ancestors is re-attached by pp_star_repair's rounds), nothing else changed */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -538,6 +540,67 @@ int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_
  * synchronises once per round run (to read the round's top count), and once more at the end. */
 int pp_star_repair(pp_ctx* ctx, int rounds, int32_t* n_nodes, int64_t* n_dropped,
                    int64_t* n_reattached, int64_t* n_recovered, int32_t* new_index);
+/* Move every query's root along its tree (build-defined, DESIGN.md §3.8 "Advancing the root"; CPU
+ * restatement tests/star_advance_ref.py): the vehicle has driven part of its plan, and the tree
+ * follows it instead of being thrown away.  Below n_q, parent, cost and elen are tree q's values
+ * before the call.
+ *
+ * The new root.  nodes: q entries in [-1, n_q).  hops: NULL, or q entries >= 0.  With hops NULL
+ * the new root is r = nodes[q]; with hops, r is the node min(hops[q], depth(nodes[q])) edges from
+ * the root on the chain root -> ... -> nodes[q] (pp_star_plan's best node with hops = 1: one edge
+ * along the planned path).  A query with nodes[q] = -1, or whose r is 0, is left alone bit for bit
+ * (rows, costs, new_index the identity), whatever rounds is.  Every chain walk on the device is
+ * bounded by n_q steps: a tree this library grew or imported has no cycle; the result for one
+ * that has is unspecified, but the call ends.
+ *
+ * The kept core, for r > 0.  Tree edges are directed Dubins edges from the child's stored pose to
+ * the parent's, so everything under r stays valid as it is, and the edges of r's proper ancestors
+ * A = parent[r], ..., node 0 (m = depth(r) nodes, the old root included) point the wrong way.
+ * K0 = the nodes i whose chain i -> ... -> 0 passes through r: r and its descendants (chains are
+ * not index-ordered).  r becomes the root: parent -1, edge cost 0, cost 0.  Every other node of
+ * K0 keeps its pose, parent and edge cost bit for bit; its cost is rebuilt from the new root
+ * down, cost'[i] = cost'[parent[i]] + elen[i], one rounded f64 add per edge, parents before
+ * children (not cost[i] - cost[r]: the sum is the invariant pp_star_forest_import checks).
+ *
+ * Re-attachment, rounds in [0, 16].  rounds = 0 stops at K0.  Otherwise the rounds are
+ * pp_star_repair's with three inputs replaced: K at the start of round 1 is K0, the costs are
+ * cost', and the tops of round 1 are all m nodes of A (the old root is one of them and keeps its
+ * stored pose, like any top).  Everything else is pp_star_repair's: a top's candidates are the
+ * star_k(k, |K|) nearest nodes of K as it stood at the start of the round by exact f64 (squared
+ * distance, index before the call); the edge top -> candidate keeps the top's pose and is feasible
+ * when the word is Some and Space::verify accepts its points followed by the candidate's point;
+ * total = cost[candidate] + edge cost, the first strict minimum in candidate order wins; a top
+ * with a choice takes parent, edge cost and cost; every dropped node that was never a top and
+ * whose chain of stored edges reaches a re-attached top is kept again with its parent and edge
+ * cost, cost = cost[parent] + elen, parents first; round r > 1: the tops are the dropped nodes,
+ * never a top before, whose parent is a top of an earlier round that found no parent.  Tops read
+ * the start-of-round state only, so their order cannot matter.  A re-attachment is not counted as
+ * a rewire.
+ *
+ * Compaction.  r goes to index 0; all other kept nodes follow in their old index order (a
+ * re-attached old root lands at index 1).  Parents are remapped and may exceed their child's
+ * index.  new_index is laid out as pp_star_revalidate's, -1 for dropped nodes, new_index[r] = 0.
+ * n_nodes, n_dropped, n_reattached, n_recovered: as pp_star_repair's (each may be NULL).  The
+ * stored start pose of the query (what pp_star_revalidate's polygon-mode root test and the forest
+ * export / import read) becomes r's pose bit for bit, and the focused sampler, which reads row 0,
+ * has the new root as its first focus from the next step on.
+ *
+ * Untouched: iterations, seeds, skipped draws, the focus (fx, fy) and its bound L, k, eta, step
+ * size, max_iter, node_evals, rewires, pp_stats and the blocked flags (a root-blocked query has
+ * one node, so only -1 or 0 is valid for it).  The old L stays admissible for the new root: the
+ * path that set it, less its driven part, is still in the tree, so L is only looser than it could
+ * be; pp_star_plan followed by pp_star_set_focus tightens it.  With rounds = 0 the scene is
+ * consulted for nothing; with rounds > 0 as in pp_star_repair.  The trees are not re-verified:
+ * that remains pp_star_revalidate's job.
+ *
+ * PP_ERR_STATE without an RRT* batch or a scene.  PP_ERR_INVALID_ARGUMENT for NULL nodes, a node
+ * outside [-1, n_q), a negative hop or rounds outside [0, 16], all checked on the host before
+ * anything is launched.  PP_ERR_STEER_OVERFLOW is possible only with rounds > 0.  A failed call
+ * leaves every tree, cost and stored start exactly as it was.  The host synchronises to read the
+ * sizes, once per round run, and once at the end (rounds = 0: no per-round reads). */
+int pp_star_advance(pp_ctx* ctx, const int32_t* nodes, const int32_t* hops, int rounds,
+                    int32_t* n_nodes, int64_t* n_dropped, int64_t* n_reattached,
+                    int64_t* n_recovered, int32_t* new_index);
 /* Goal connection (build-defined; CPU restatement tests/star_goal_ref.py).  The
  * goal edge of tree node m: the goal (gx, gy, gyaw) is the child and keeps its yaw, node m is the
  * parent — Dubins from the goal pose to the node's stored pose; feasible when the word is Some and

@@ -11,6 +11,7 @@
 //                      pp_star_revalidate
 //   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
 //   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
+//   pp_advance.cpp  pp_star_advance: a node becomes the root; the repair's rounds on its ancestors
 //   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
 //   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_star_chain_segments,
 //                    pp_segments_sample
@@ -452,7 +453,7 @@ struct Reval {
     DBuf<int> lvl, wpar, tops, tslot, tcnt, near;
     DBuf<double> wcost, welen, tcost;
     DBuf<RepairRec> rrec;
-    // pp_star_prune only (PruneArgs)
+    // pp_star_prune (PruneArgs); pp_star_advance's nodes, hops and roots (AdvanceArgs)
     DBuf<int> keep;
 };
 

@@ -236,7 +236,9 @@ __global__ __launch_bounds__(kRvThreads) void reval_write_kernel(RevalArgs a) {
 
 // The three stages of a revalidation, so that pp_star_repair can work between the jump and the
 // compaction: the edge test into a.v[0], the doubling into a.v[passes & 1], the compaction of the
-// nodes rv_keep keeps in v.
+// nodes rv_keep keeps in v.  The compaction is its scan, its gather and its write; the scan and
+// the write are launched on their own by pp_star_advance, around a gather that puts the new root
+// first (pp_k_advance.hip).
 hipError_t launch_reval_edges(hipStream_t s, const SceneDev& sc, const RevalArgs& a) {
     if (a.total <= 0 || a.slice <= 0) return hipErrorInvalidValue;
     const int limit = walk_grid_limit(kWalkBatchPlan, sc);
@@ -260,16 +262,25 @@ hipError_t launch_reval_jump(hipStream_t s, const RevalArgs& a, int passes) {
     return hipGetLastError();
 }
 
-hipError_t launch_reval_compact(hipStream_t s, const RevalArgs& a, const unsigned* v) {
-    const int g = (a.total + kRvThreads - 1) / kRvThreads;
+hipError_t launch_reval_scan(hipStream_t s, const RevalArgs& a, const unsigned* v, const int* koff) {
     const int nb = (a.total + kRvScan - 1) / kRvScan;
-    const int* koff = a.any_order ? a.off : nullptr;
     reval_count_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum, koff, a.Q);
     reval_bscan_kernel<<<1, kRvScan, 0, s>>>(a.bsum, nb);
     reval_pos_kernel<<<nb, kRvScan, 0, s>>>(v, a.total, a.bsum, a.pos, koff, a.Q);
-    reval_gather_kernel<<<g, kRvThreads, 0, s>>>(a, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_reval_write(hipStream_t s, const RevalArgs& a) {
     reval_write_kernel<<<(std::max(a.total, a.Q) + kRvThreads - 1) / kRvThreads, kRvThreads, 0, s>>>(a);
     return hipGetLastError();
+}
+
+hipError_t launch_reval_compact(hipStream_t s, const RevalArgs& a, const unsigned* v) {
+    const int g = (a.total + kRvThreads - 1) / kRvThreads;
+    hipError_t e = launch_reval_scan(s, a, v, a.any_order ? a.off : nullptr);
+    if (e != hipSuccess) return e;
+    reval_gather_kernel<<<g, kRvThreads, 0, s>>>(a, v);
+    return launch_reval_write(s, a);
 }
 
 hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs& a, int passes) {

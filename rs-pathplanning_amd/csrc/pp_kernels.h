@@ -461,6 +461,11 @@ hipError_t launch_revalidate(hipStream_t s, const SceneDev& sc, const RevalArgs&
 hipError_t launch_reval_edges(hipStream_t s, const SceneDev& sc, const RevalArgs& a);
 hipError_t launch_reval_jump(hipStream_t s, const RevalArgs& a, int passes);
 hipError_t launch_reval_compact(hipStream_t s, const RevalArgs& a, const unsigned* v);
+// ... and the compaction's two ends around its gather, for a caller with a gather of its own
+// (pp_star_advance): the exclusive scan of rv_keep(v, g, koff, Q) into a.pos, and the staged rows
+// back into the trees with the new sizes
+hipError_t launch_reval_scan(hipStream_t s, const RevalArgs& a, const unsigned* v, const int* koff);
+hipError_t launch_reval_write(hipStream_t s, const RevalArgs& a);
 
 // Repair (pp_star_repair, pp_k_repair.hip): between the jump and the compaction
 // of an RRT* forest's revalidation, dropped subtrees are hung under kept nodes again, in rounds.
@@ -507,6 +512,27 @@ hipError_t launch_repair_knn(hipStream_t s, const RepairArgs& a, int ntops);
 // walk, choose
 hipError_t launch_repair_slice(hipStream_t s, const SceneDev& sc, const RepairArgs& a, int t0,
                                int t1);
+
+// Advance (pp_star_advance, pp_k_advance.hip; DESIGN.md §3.8 "Advancing the root"): node root[q]
+// of tree q becomes its root.  The repair's staged arrays (rp) hold the kept core and its rebuilt
+// costs; the repair's own rounds then run on them with the old root's chain as round 1's tops, and
+// a gather of this unit puts the new root first.  Nothing is written into the trees before
+// launch_reval_write.
+struct AdvanceArgs {
+    RepairArgs rp;
+    const int* nodes = nullptr;  // [Q] the caller's nodes, -1: the query stays
+    const int* hops = nullptr;   // [Q] edges from the root along the chain to nodes[q] (null: all)
+    int* root = nullptr;         // [Q] the new root's index before the call, 0: the query stays
+    double* starts = nullptr;    // [3Q] the stored roots (Forest::d_starts)
+};
+enum : int { kAdvanceCore = 0, kAdvanceTops, kAdvanceKeep, kAdvanceGather, kAdvanceStarts };
+// one stage: core (the walk to root[q], the keep words of its subtree through the doubling of
+// `passes` passes, the staged copies and the costs rebuilt level by level from the new root),
+// tops (round 1's: the proper ancestors of root[q], counted in rec->ntops[1]), keep (the words
+// launch_reval_scan(koff = null) keeps by, into rp.vout), gather (the kept rows staged with the
+// new root first) and starts (row 0 into the stored start of every advanced query, unless a
+// steer overflowed)
+hipError_t launch_advance_stage(hipStream_t s, const AdvanceArgs& a, int stage, int passes);
 
 // Prune (pp_star_prune, pp_k_prune.hip; DESIGN.md §3.7 "Pruning by the focus bound"): the keep
 // words of an RRT* forest by its queries' focus bounds, in front of launch_reval_jump and

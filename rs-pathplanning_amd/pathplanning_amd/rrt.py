@@ -929,6 +929,38 @@ class RRTStarBatch:
         self.last_recovered = rec.value
         return n, new_index[:total]
 
+    def advance(self, nodes, hops=None, rounds: int = 0, n_old=None):
+        """Move every query's root along its tree (pp_star_advance): the vehicle has driven, and
+        the tree follows it.  ``nodes``: one node per query, -1 to leave a query alone.  ``hops``
+        (None, a scalar for all, or one per query): the new root is the node that many edges from
+        the root on the chain root -> ``nodes[q]`` (clamped to the chain); None: ``nodes[q]``
+        itself.  ``advance(best_node, hops=1)`` follows a plan by one edge.  The subtree under the
+        new root is kept with its costs rebuilt from it; the rest hung from the new root's
+        ancestors, whose edges point the wrong way: with ``rounds`` (0..16) > 0 those ancestors
+        are the first tops of ``repair``'s rounds, which hang back what still finds a feasible
+        edge.  The new root gets index 0, the other kept nodes follow in their old order.
+        Counters, seeds and the focus stay (the old bound stays admissible; ``plan(goals,
+        focus=True)`` tightens it).  Returns (n_nodes, new_index) as ``revalidate`` does and sets
+        ``last_dropped``, ``last_reattached`` and ``last_recovered``."""
+        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
+        total = int(n_old.sum(dtype=np.int64))
+        new_index = np.zeros(max(total, 1), dtype=np.int32)
+        n = np.zeros(self.q, dtype=np.int32)
+        dropped, rea, rec = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        ip = C.POINTER(C.c_int32)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
+        if hops is not None:
+            hops = np.ascontiguousarray(np.broadcast_to(np.asarray(hops, dtype=np.int32),
+                                                        (self.q,)))
+        _ffi.check(_ffi.lib().pp_star_advance(
+            self.ctx.handle, nodes.ctypes.data_as(ip),
+            None if hops is None else hops.ctypes.data_as(ip), int(rounds), n.ctypes.data_as(ip),
+            C.byref(dropped), C.byref(rea), C.byref(rec), new_index.ctypes.data_as(ip)))
+        self.last_dropped = dropped.value
+        self.last_reattached = rea.value
+        self.last_recovered = rec.value
+        return n, new_index[:total]
+
     def set_space(self, space: Space, repair_rounds: int | None = None):
         """Replace the scene of the batch and keep every tree where it still holds: uploads
         ``space`` into the batch's context and revalidates — with ``repair_rounds`` given, by
