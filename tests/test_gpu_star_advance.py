@@ -77,24 +77,32 @@ def _targets(osc, trees, goal, where):
 PER_SLOT = ("iterations", "seeds", "node_evals", "rewires", "focus_xy", "focus_bound", "skipped")
 
 
-def _advance_checked(b, osc, k, nodes, hops, rounds):
+def _advance_checked(b, osc, k, nodes, hops, rounds, check=None):
     """b.advance(nodes, hops, rounds): everything the call returns and leaves behind against the
-    restatement of the state exported just before it.  Returns the restatements."""
-    before = _trees(b)
+    restatement of the state exported just before it.  `check`: the queries that are restated and
+    whose rows are compared (all; a subset needs rounds = 0, where the batch's counters are known
+    without a restatement).  Returns the restatements (a dict by query when `check` is given)."""
+    qs = list(range(b.q)) if check is None else [int(q) for q in check]
+    assert check is None or rounds == 0
+    n_old = b.state()[0]
+    before = {q: b.tree(q, n_old[q]) for q in qs}
     st0 = b.export_forest()
-    el = _elens(st0)
+    assert np.array_equal(st0["off"][1:] - st0["off"][:-1], n_old)
+    off = st0["off"]
+    el = {q: st0["edge_cost"][off[q]:off[q + 1]] for q in qs}
     hq = (lambda q: None) if hops is None else (lambda q: int(np.broadcast_to(hops, (b.q,))[q]))
-    exp = [adv.advance(osc, before[q], el[q], k, int(nodes[q]), hq(q), rounds)
-           for q in range(b.q)]
-    n_old = st0["off"][1:] - st0["off"][:-1]
+    exp = {q: adv.advance(osc, before[q], el[q], k, int(nodes[q]), hq(q), rounds) for q in qs}
     state0, focus0 = b.state(), b.focus_state()
     n_new, new_index = b.advance(nodes, hops=hops, rounds=rounds)
-    off = st0["off"]
     assert len(new_index) == off[-1]
-    assert np.array_equal(n_new, [e["kept"] for e in exp]), (n_new, [e["rounds"] for e in exp])
+    assert np.array_equal(n_new[qs], [exp[q]["kept"] for q in qs]), (
+        n_new[qs], [exp[q]["rounds"] for q in qs])
     assert b.last_dropped == int((n_old - n_new).sum())
-    assert b.last_reattached == sum(e["reattached"] for e in exp)
-    assert b.last_recovered == sum(e["recovered"] for e in exp)
+    if check is None:
+        assert b.last_reattached == sum(e["reattached"] for e in exp.values())
+        assert b.last_recovered == sum(e["recovered"] for e in exp.values())
+    else:
+        assert b.last_reattached == 0 and b.last_recovered == 0
     state1 = b.state()
     assert np.array_equal(state1[0], n_new)
     for s0, s1 in zip(state0[1:], state1[1:]):
@@ -104,35 +112,37 @@ def _advance_checked(b, osc, k, nodes, hops, rounds):
     st1 = b.export_forest()
     for key in PER_SLOT:
         assert np.array_equal(st0[key], st1[key]), key
-    el1 = _elens(st1)
-    for q, e in enumerate(exp):
+    off1 = st1["off"]
+    for q, e in exp.items():
         got_index = new_index[off[q]:off[q + 1]]
         assert np.array_equal(got_index, e["new_index"]), (
             q, np.flatnonzero(got_index != e["new_index"])[:10], adv.min_gap(e))
         x, y, yaw, par, cost = b.tree(q, n_new[q])
+        el1 = st1["edge_cost"][off1[q]:off1[q + 1]]
         ex, ey, eyaw, epar, ecost = e["tree"]
         assert np.array_equal(x, ex) and np.array_equal(y, ey) and np.array_equal(yaw, eyaw), q
         assert np.array_equal(par, epar), (q, np.flatnonzero(par != epar)[:10], adv.min_gap(e))
         k0 = np.zeros(e["kept"], dtype=bool)
         k0[e["new_index"][e["keep0"]]] = True
         if e["identity"]:  # bit for bit
-            _assert_exact((x, y, yaw, par, cost, el1[q]), before[q] + (el[q],))
+            _assert_exact((x, y, yaw, par, cost, el1), before[q] + (el[q],))
         assert np.array_equal(cost[k0].view(np.uint64), ecost[k0].view(np.uint64)), q
-        assert np.array_equal(el1[q][k0].view(np.uint64), e["elen"][k0].view(np.uint64)), q
+        assert np.array_equal(el1[k0].view(np.uint64), e["elen"][k0].view(np.uint64)), q
         assert np.allclose(cost[~k0], ecost[~k0], rtol=COST_RTOL, atol=0.0), q
-        assert np.allclose(el1[q][~k0], e["elen"][~k0], rtol=COST_RTOL, atol=0.0), q
-    return exp
+        assert np.allclose(el1[~k0], e["elen"][~k0], rtol=COST_RTOL, atol=0.0), q
+    return [exp[q] for q in range(b.q)] if check is None else exp
 
 
-def _continue_checked(oracle_mod, b, osc, exp, seeds, it0, n_steps, k, eta):
-    """n_steps more lockstep steps against orc_star_extend continued from the restated trees"""
+def _continue_checked(oracle_mod, b, osc, exp, seeds, it0, n_steps, k, eta, queries=None):
+    """n_steps more lockstep steps against orc_star_extend continued from the restated trees
+    (`queries`: the ones compared; all)"""
     rw0 = b.state()[3]
     b.extend(n_steps)
     n, it, _, rw = b.state()
     assert (it == it0 + n_steps).all()
-    for q, e in enumerate(exp):
-        t = e["tree"]
-        tr = ref.oracle_tree((t[0][0], t[1][0], t[2][0]), t, e["elen"], n_steps)
+    for q in (range(len(exp)) if queries is None else queries):
+        t = exp[q]["tree"]
+        tr = ref.oracle_tree((t[0][0], t[1][0], t[2][0]), t, exp[q]["elen"], n_steps)
         _, erw, _, _ = oracle_mod.star_extend(osc, tr, int(seeds[q]), it0, n_steps, k, eta)
         _assert_same(b.tree(q, n[q]), tr.star_arrays())
         assert rw[q] - rw0[q] == erw, q
