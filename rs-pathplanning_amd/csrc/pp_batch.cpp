@@ -114,6 +114,51 @@ int Forest::copy_state(pp_ctx* c, int32_t* n_nodes, int64_t* iterations, int64_t
     return PP_OK;
 }
 
+int Forest::sizes(pp_ctx* c, std::vector<int>* hn, int64_t* total, const int32_t* nodes,
+                  const char* bad_node) const {
+    hn->assign((size_t)Q, 0);
+    PP_HIP(hipMemcpyAsync(hn->data(), n.p, Q * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PP_HIP(hipStreamSynchronize(c->stream));
+    int64_t sum = 0;
+    for (int q = 0; q < Q; ++q) {
+        sum += (*hn)[(size_t)q];
+        if (nodes && (nodes[q] < -1 || nodes[q] >= (*hn)[(size_t)q]))
+            return set_err(PP_ERR_INVALID_ARGUMENT, bad_node);
+    }
+    if (total) *total = sum;
+    return PP_OK;
+}
+
+int Forest::reval_inputs(pp_ctx* c, std::vector<int>* hn, std::vector<uint8_t>* blk, bool* any) const {
+    hipStream_t st = c->stream;
+    hn->assign((size_t)Q, 0);
+    std::vector<double> starts(3 * (size_t)Q);
+    PP_HIP(hipMemcpyAsync(hn->data(), n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(starts.data(), d_starts.p, starts.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    // the roots that fail verify in the scene as it is now (Forest::init)
+    blk->assign((size_t)Q, 0);
+    *any = false;
+    if (c->scene.polygons())
+        for (int q = 0; q < Q; ++q) {
+            (*blk)[(size_t)q] = c->scene.point_ok(starts[3 * (size_t)q], starts[3 * (size_t)q + 1]) ? 0 : 1;
+            *any |= (*blk)[(size_t)q] != 0;
+        }
+    return PP_OK;
+}
+
+int Forest::reval_outputs(pp_ctx* c, const std::vector<uint8_t>& blk, bool any, int32_t* n_nodes) {
+    hipStream_t st = c->stream;
+    if (any) {
+        PP_HIP(blocked.reserve(Q));
+        PP_HIP(hipMemcpy(blocked.p, blk.data(), Q, hipMemcpyHostToDevice));
+    }
+    any_blocked = any;
+    if (n_nodes) PP_HIP(hipMemcpyAsync(n_nodes, n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
+    PP_HIP(hipStreamSynchronize(st));
+    return PP_OK;
+}
+
 int Forest::export_tree(pp_ctx* c, int query, double* ox, double* oy, double* oyaw, int32_t* oparent,
                         int64_t ocap, int64_t* n_out, const double* extra, double* extra_out) const {
     if (query < 0 || query >= Q) return set_err(PP_ERR_INVALID_ARGUMENT, "query out of range");
@@ -604,10 +649,9 @@ int pp_star_new(pp_ctx* ctx, int q, const double* starts, const uint64_t* seeds,
 
 int pp_star_extend(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t* n_accepted,
                    int64_t* n_rewires) {
-    int r = check_ctx(ctx, true, false);
+    int r = star_ready(ctx);
     if (r) return r;
     StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     if (n_steps < 0) return set_err(PP_ERR_INVALID_ARGUMENT, "n_steps < 0");
     const bool tot = n_iterations || n_accepted || n_rewires;
     int64_t it0 = 0, n0 = 0, w0 = 0, it1 = 0, n1 = 0, w1 = 0;
@@ -648,19 +692,17 @@ int pp_star_extend(pp_ctx* ctx, int64_t n_steps, int64_t* n_iterations, int64_t*
 
 int pp_star_state(pp_ctx* ctx, int32_t* n_nodes, int64_t* iterations, int64_t* node_evals,
                   int64_t* rewires) {
-    int r = check_ctx(ctx, true, false);
+    int r = star_ready(ctx);
     if (r) return r;
     const StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     return s.f.copy_state(ctx, n_nodes, iterations, node_evals, s.rew.p, rewires);
 }
 
 int pp_star_tree_export(pp_ctx* ctx, int query, double* x, double* y, double* yaw,
                         int32_t* parent, double* cost, int64_t cap, int64_t* n) {
-    int r = check_ctx(ctx, true, false);
+    int r = star_ready(ctx);
     if (r) return r;
     const StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     return s.f.export_tree(ctx, query, x, y, yaw, parent, cap, n, s.cost.p, cost);
 }
 
@@ -668,9 +710,8 @@ static_assert(kStarFocusDraws == PP_STAR_FOCUS_DRAWS && kStarFocusDraws % 64 == 
               "the kernel's draw limit is the header's, in whole wave rounds");
 
 int pp_star_set_focus(pp_ctx* ctx, const double* fxy, const double* bound) {
-    if (!ctx) return set_err(PP_ERR_INVALID_ARGUMENT, "null context");
+    if (int r = star_ready(ctx)) return r;
     StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     if (!fxy != !bound)
         return set_err(PP_ERR_INVALID_ARGUMENT, "focus points and bounds: both or neither");
     const int q = s.f.Q;
@@ -692,9 +733,8 @@ int pp_star_set_focus(pp_ctx* ctx, const double* fxy, const double* bound) {
 }
 
 int pp_star_get_focus(pp_ctx* ctx, double* fxy, double* bound, int64_t* skipped) {
-    if (!ctx) return set_err(PP_ERR_INVALID_ARGUMENT, "null context");
+    if (int r = star_ready(ctx)) return r;
     const StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     const int q = s.f.Q;
     hipStream_t st = ctx->stream;
     if (fxy) PP_HIP(hipMemcpyAsync(fxy, s.fxy.p, 2 * (size_t)q * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -30,12 +30,15 @@ int check_coords(const double* v, int64_t n, int64_t stride, const char* what) {
     return PP_OK;
 }
 
+int star_ready(pp_ctx* c) {
+    int r = check_ctx(c, true, false);
+    if (r) return r;
+    if (!c->star.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
+    return PP_OK;
+}
+
 int ensure_events(pp_ctx* c, size_t count) {
-    while (c->prof.ev.size() < count) {
-        hipEvent_t e;
-        PP_HIP(hipEventCreate(&e));
-        c->prof.ev.push_back(e);
-    }
+    PP_HIP(c->prof.ev.reserve(count));
     return PP_OK;
 }
 

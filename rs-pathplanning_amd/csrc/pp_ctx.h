@@ -9,9 +9,9 @@
 //                     pp_star_paths
 //   pp_revalidate.cpp  a tree across a scene change: pp_rrt_revalidate, pp_batch_revalidate,
 //                      pp_star_revalidate
-//   pp_repair.cpp   pp_star_repair: that revalidation with re-attachment rounds
+//   pp_repair.cpp   the re-attachment rounds: pp_star_repair (that revalidation with the rounds) and
+//                   pp_star_advance (a node becomes the root; the rounds on its ancestors)
 //   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
-//   pp_advance.cpp  pp_star_advance: a node becomes the root; the repair's rounds on its ancestors
 //   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
 //   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_star_chain_segments,
 //                    pp_segments_sample
@@ -364,6 +364,17 @@ struct Forest {
     // the per-query counters (a null output is skipped)
     int copy_state(pp_ctx* c, int32_t* n_nodes, int64_t* iterations, int64_t* node_evals,
                    const int64_t* extra = nullptr, int64_t* extra_out = nullptr) const;
+    // the trees' sizes on the host after one synchronise, and (may be null) their sum.  nodes (may
+    // be null): one node per query, each -1 or a node of its tree, else PP_ERR_INVALID_ARGUMENT
+    // with the caller's message
+    int sizes(pp_ctx* c, std::vector<int>* hn, int64_t* total = nullptr,
+              const int32_t* nodes = nullptr, const char* bad_node = nullptr) const;
+    // what a revalidation of the forest reads first: the trees' sizes and, in polygon mode, the
+    // roots that fail verify in the scene as it is now (*any: at least one does) ...
+    int reval_inputs(pp_ctx* c, std::vector<int>* hn, std::vector<uint8_t>* blk, bool* any) const;
+    // ... and what it leaves behind: the derived blocked[] and the sizes for the caller (may be
+    // null), synchronised
+    int reval_outputs(pp_ctx* c, const std::vector<uint8_t>& blk, bool any, int32_t* n_nodes);
     // one tree's rows (*n_out: its nodes, also when ocap is too small)
     int export_tree(pp_ctx* c, int query, double* ox, double* oy, double* oyaw, int32_t* oparent,
                     int64_t ocap, int64_t* n_out, const double* extra = nullptr,
@@ -478,10 +489,32 @@ struct Shortcut {
 // the most (i, j) pairs one pp_star_shortcut call steers
 constexpr int64_t kShortcutMaxPairs = (int64_t)1 << 26;
 
+// ---- HIP events with an owner: created on demand, destroyed with it (a context's profiling
+// events; one call's timing events, whichever way the call returns)
+struct Events {
+    std::vector<hipEvent_t> ev;
+    Events() = default;
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    hipError_t reserve(size_t count) {  // at least `count` events
+        while (ev.size() < count) {
+            hipEvent_t e = nullptr;
+            if (hipError_t r = hipEventCreate(&e)) return r;
+            ev.push_back(e);
+        }
+        return hipSuccess;
+    }
+    hipEvent_t& operator[](size_t i) { return ev[i]; }
+    hipEvent_t* data() { return ev.data(); }
+    ~Events() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+
 // ---- profiling
 struct Profiling {
     bool on = false;
-    std::vector<hipEvent_t> ev;  // 4 per window or batch step, 8 per RRT* step
+    Events ev;  // 4 per window or batch step, 8 per RRT* step
     double nn_scan_ms = 0.0, steer_ms = 0.0, finish_ms = 0.0, finalize_ms = 0.0, prep_ms = 0.0,
            insert_ms = 0.0;
     int64_t nn_scan_launches = 0, steer_launches = 0, finish_launches = 0;
@@ -501,10 +534,6 @@ struct Profiling {
         if (cf_tally.p && hipMemsetAsync(cf_tally.p, 0, cf_tally.n * sizeof(long long), stream) != hipSuccess)
             return PP_ERR_HIP;
         return hipStreamSynchronize(stream) == hipSuccess ? PP_OK : PP_ERR_HIP;
-    }
-    ~Profiling() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -544,6 +573,8 @@ struct pp_ctx {
 namespace ppamd {
 
 int check_ctx(pp_ctx* c, bool need_scene, bool need_rrt);
+// check_ctx with a scene, and an RRT* batch (pp_star_new succeeded): every pp_star_* entry point
+int star_ready(pp_ctx* c);
 // The coordinates v[0], v[stride], ... (n of them; a null v passes) are finite and at most
 // PP_COORD_MAX in magnitude, else PP_ERR_INVALID_ARGUMENT naming `what`: every entry point that
 // takes positions runs this on the host before it launches anything (pp_coord_check's test).
@@ -573,7 +604,7 @@ int paths_write(pp_ctx* c, const SceneDev& sd, PathsArgs a, const CfLines& lines
                 const int* items, int k, bool star, double* x, double* y, int64_t total,
                 double* len_host = nullptr);
 // The two host halves of a revalidation around its launches (pp_revalidate.cpp), shared with
-// pp_star_repair (pp_repair.cpp).  reval_setup: the buffers (the steer slice's for at least
+// pp_repair.cpp and pp_prune.cpp.  reval_setup: the buffers (the steer slice's for at least
 // min_tasks tasks; min_tasks < 0: no steer slice and no literal pool, pp_star_prune's verdicts
 // need neither), the offsets and blocked roots on the device, the kernel arguments and the
 // doubling passes, for Q trees of hn[q] nodes in the rows tr (tree q at q * cap).  reval_finish:
@@ -583,10 +614,5 @@ int reval_setup(pp_ctx* c, const TreeDev& tr, int Q, size_t cap, const std::vect
                 const uint8_t* blocked, int* d_n, bool any_order, double* cost, double* elen,
                 int min_tasks, RevalArgs* a, int* passes);
 int reval_finish(pp_ctx* c, const RevalArgs& a, int64_t* kept, int32_t* new_index);
-// what pp_star_revalidate and pp_star_repair read first: the trees' sizes and, in polygon mode,
-// the roots that fail verify in the scene as it is now (*any: at least one does)
-int star_reval_inputs(pp_ctx* c, std::vector<int>* hn, std::vector<uint8_t>* blk, bool* any);
-// ... and what both leave behind: the derived blocked[] and the sizes for the caller
-int star_reval_outputs(pp_ctx* c, const std::vector<uint8_t>& blk, bool any, int32_t* n_nodes);
 
 }  // namespace ppamd

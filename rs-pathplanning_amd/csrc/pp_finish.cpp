@@ -382,13 +382,10 @@ namespace ppamd {
 int paths_items(pp_ctx* c, const Forest& f, const int32_t* nodes, int* k) {
     const int Q = f.Q;
     hipStream_t st = c->stream;
-    std::vector<int> hn(Q), qi, nd, slot(Q, -1);
-    PP_HIP(hipMemcpyAsync(hn.data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
+    std::vector<int> hn, qi, nd, slot(Q, -1);
+    if (int r = f.sizes(c, &hn, nullptr, nodes, "node index outside its query's tree")) return r;
     for (int q = 0; q < Q; ++q) {
         if (nodes[q] == -1) continue;
-        if (nodes[q] < 0 || nodes[q] >= hn[q])
-            return set_err(PP_ERR_INVALID_ARGUMENT, "node index outside its query's tree");
         slot[q] = (int)qi.size();
         qi.push_back(q);
         nd.push_back(nodes[q]);
@@ -666,9 +663,8 @@ int pp_batch_plan(pp_ctx* ctx, int32_t* best_node, double* length, int32_t* n_po
     const int Q = b.f.Q;
     hipStream_t st = ctx->stream;
     // the accepted nodes of every query (1 .. n_q - 1, rrt.rs:591), flattened
-    std::vector<int> hn(Q), off((size_t)Q + 1, 0);
-    PP_HIP(hipMemcpyAsync(hn.data(), b.f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
+    std::vector<int> hn, off((size_t)Q + 1, 0);
+    if ((r = b.f.sizes(ctx, &hn))) return r;
     int64_t total = 0;
     for (int q = 0; q < Q; ++q) {
         off[q] = (int)total;

@@ -304,9 +304,8 @@ int forest_import(pp_ctx* c, const Target& t, const int32_t* queries, int m,
 }
 
 int star_target(pp_ctx* ctx, Target* t) {
-    int rc = check_ctx(ctx, false, false);
+    int rc = star_ready(ctx);
     if (rc) return rc;
-    if (!ctx->star.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     t->f = &ctx->star.f;
     t->s = &ctx->star;
     return PP_OK;

@@ -12,22 +12,16 @@ extern "C" {
 
 int pp_star_prune(pp_ctx* ctx, const int32_t* keep, int32_t* n_nodes, int64_t* n_dropped,
                   int32_t* new_index) {
-    int rc = check_ctx(ctx, true, false);
+    int rc = star_ready(ctx);
     if (rc) return rc;
     StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "no RRT* batch to prune: pp_star_new has not been called");
     Forest& f = s.f;
     const int Q = f.Q;
     hipStream_t st = ctx->stream;
-    std::vector<int> hn((size_t)Q, 0);
-    PP_HIP(hipMemcpyAsync(hn.data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
+    std::vector<int> hn;
     int64_t kept = 0, total = 0;
-    for (int q = 0; q < Q; ++q) {
-        total += hn[(size_t)q];
-        if (keep && (keep[q] < -1 || keep[q] >= hn[(size_t)q]))
-            return set_err(PP_ERR_INVALID_ARGUMENT, "a keep node must be -1 or a node of its query's tree");
-    }
+    if ((rc = f.sizes(ctx, &hn, &total, keep, "a keep node must be -1 or a node of its query's tree")))
+        return rc;
     // parents in any order, cost and elen travel with the rows, mark / stamp stay
     // (pp_star_revalidate's); no blocked roots: the scene is not consulted, blocked[] stays
     PruneArgs p;

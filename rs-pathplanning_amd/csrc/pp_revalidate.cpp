@@ -114,42 +114,6 @@ int reval_finish(pp_ctx* c, const RevalArgs& a, int64_t* kept, int32_t* new_inde
     return PP_OK;
 }
 
-int star_reval_inputs(pp_ctx* c, std::vector<int>* hn, std::vector<uint8_t>* blk, bool* any) {
-    Forest& f = c->star.f;
-    const int Q = f.Q;
-    hipStream_t st = c->stream;
-    hn->assign((size_t)Q, 0);
-    std::vector<double> starts(3 * (size_t)Q);
-    PP_HIP(hipMemcpyAsync(hn->data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipMemcpyAsync(starts.data(), f.d_starts.p, starts.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
-    // the roots that fail verify in the scene as it is now (Forest::init)
-    blk->assign((size_t)Q, 0);
-    *any = false;
-    if (c->scene.polygons())
-        for (int q = 0; q < Q; ++q) {
-            (*blk)[(size_t)q] = c->scene.point_ok(starts[3 * (size_t)q], starts[3 * (size_t)q + 1]) ? 0 : 1;
-            *any |= (*blk)[(size_t)q] != 0;
-        }
-    return PP_OK;
-}
-
-int star_reval_outputs(pp_ctx* c, const std::vector<uint8_t>& blk, bool any, int32_t* n_nodes) {
-    Forest& f = c->star.f;
-    const int Q = f.Q;
-    hipStream_t st = c->stream;
-    if (any) {
-        PP_HIP(f.blocked.reserve(Q));
-        PP_HIP(hipMemcpy(f.blocked.p, blk.data(), Q, hipMemcpyHostToDevice));
-    }
-    f.any_blocked = any;
-    if (n_nodes) {
-        PP_HIP(hipMemcpyAsync(n_nodes, f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-        PP_HIP(hipStreamSynchronize(st));
-    }
-    return PP_OK;
-}
-
 }  // namespace ppamd
 
 namespace {
@@ -157,15 +121,13 @@ namespace {
 // The device pass over Q trees of hn[q] nodes in the rows tr (tree q at q * cap): *kept the nodes
 // that stay over all trees; new_index (may be null) the sum of hn entries.  blocked (host, may be
 // null): the roots that fail verify.  d_n (may be null): the trees' node counts on the device.
-// any_order with the cost / elen rows: an RRT* forest (RevalArgs), else false and null.
 // One synchronisation; on PP_ERR_STEER_OVERFLOW the trees are unmodified.
 int reval_run(pp_ctx* c, const SceneDev& sc, const TreeDev& tr, int Q, size_t cap,
               const std::vector<int>& hn, const uint8_t* blocked, int* d_n, int64_t* kept,
-              int32_t* new_index, bool any_order = false, double* cost = nullptr,
-              double* elen = nullptr) {
+              int32_t* new_index) {
     RevalArgs a;
     int passes = 0, rc;
-    if ((rc = reval_setup(c, tr, Q, cap, hn, blocked, d_n, any_order, cost, elen, 0, &a, &passes)))
+    if ((rc = reval_setup(c, tr, Q, cap, hn, blocked, d_n, false, nullptr, nullptr, 0, &a, &passes)))
         return rc;
     PP_HIP(launch_revalidate(c->stream, sc, a, passes));
     return reval_finish(c, a, kept, new_index);
@@ -224,35 +186,19 @@ int pp_batch_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32
     if (!b.valid && !b.stale) return set_err(PP_ERR_STATE, "no batch to revalidate: pp_batch_new has not been called");
     Forest& f = b.f;
     const int Q = f.Q;
-    hipStream_t st = ctx->stream;
-    std::vector<int> hn((size_t)Q);
-    std::vector<double> starts(3 * (size_t)Q);
-    PP_HIP(hipMemcpyAsync(hn.data(), f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipMemcpyAsync(starts.data(), f.d_starts.p, starts.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
-    // the roots that fail verify in the scene as it is now (Forest::init)
-    std::vector<uint8_t> blk((size_t)Q, 0);
+    std::vector<int> hn;
+    std::vector<uint8_t> blk;
     bool any = false;
-    if (ctx->scene.polygons())
-        for (int q = 0; q < Q; ++q) {
-            blk[(size_t)q] = ctx->scene.point_ok(starts[3 * (size_t)q], starts[3 * (size_t)q + 1]) ? 0 : 1;
-            any |= blk[(size_t)q] != 0;
-        }
+    if ((rc = f.reval_inputs(ctx, &hn, &blk, &any))) return rc;
     SceneDev sc = ctx->scene.dev(f.step, false);
     int64_t kept = 0, total = 0;
     for (int q = 0; q < Q; ++q) total += hn[(size_t)q];
     if ((rc = reval_run(ctx, sc, f.tree_dev(), Q, (size_t)f.cap, hn, any ? blk.data() : nullptr,
                         f.n.p, &kept, new_index)))
         return rc;
-    if (any) {
-        PP_HIP(f.blocked.reserve(Q));
-        PP_HIP(hipMemcpy(f.blocked.p, blk.data(), Q, hipMemcpyHostToDevice));
-    }
-    f.any_blocked = any;
     // the verdict cache holds the old scene's verdicts
-    PP_HIP(hipMemsetAsync(b.itprev.p, 0x80, Q * sizeof(int64_t), st));
-    if (n_nodes) PP_HIP(hipMemcpyAsync(n_nodes, f.n.p, Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
+    PP_HIP(hipMemsetAsync(b.itprev.p, 0x80, Q * sizeof(int64_t), ctx->stream));
+    if ((rc = f.reval_outputs(ctx, blk, any, n_nodes))) return rc;
     b.stale = false;
     b.valid = true;
     if (n_dropped) *n_dropped = total - kept;
@@ -260,28 +206,8 @@ int pp_batch_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32
 }
 
 int pp_star_revalidate(pp_ctx* ctx, int32_t* n_nodes, int64_t* n_dropped, int32_t* new_index) {
-    int rc = check_ctx(ctx, true, false);
-    if (rc) return rc;
-    StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "no RRT* batch to revalidate: pp_star_new has not been called");
-    Forest& f = s.f;
-    const int Q = f.Q;
-    std::vector<int> hn;
-    std::vector<uint8_t> blk;
-    bool any = false;
-    if ((rc = star_reval_inputs(ctx, &hn, &blk, &any))) return rc;
-    SceneDev sc = ctx->scene_dev();  // the scene of the batch's own steer rounds (star_args)
-    sc.step_size = f.step;
-    int64_t kept = 0, total = 0;
-    for (int q = 0; q < Q; ++q) total += hn[(size_t)q];
-    // a rewired node hangs under the later node that rewired it: parents in any order; cost and
-    // elen travel with the rows, mark / stamp stay (reval_write_kernel)
-    if ((rc = reval_run(ctx, sc, f.tree_dev(), Q, (size_t)f.cap, hn, any ? blk.data() : nullptr,
-                        f.n.p, &kept, new_index, true, s.cost.p, s.elen.p)))
-        return rc;
-    if ((rc = star_reval_outputs(ctx, blk, any, n_nodes))) return rc;
-    if (n_dropped) *n_dropped = total - kept;
-    return PP_OK;
+    // the repair (pp_repair.cpp) without a re-attachment round: its edge test, jump and compaction
+    return pp_star_repair(ctx, 0, n_nodes, n_dropped, nullptr, nullptr, new_index);
 }
 
 }  // extern "C"

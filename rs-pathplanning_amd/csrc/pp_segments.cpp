@@ -161,10 +161,9 @@ extern "C" {
 int pp_star_path_segments(pp_ctx* ctx, const double* goals, const int32_t* nodes, int reverse,
                           int64_t* off, const pp_path_segments* seg, int64_t cap,
                           int64_t* n_total, double* length, uint8_t* ok) {
-    int r = check_ctx(ctx, true, false);
+    int r = star_ready(ctx);
     if (r) return r;
     StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     if (!goals || !nodes || !off || !n_total)
         return set_err(PP_ERR_INVALID_ARGUMENT, "null goals, nodes, off or n_total");
     if (reverse != 0 && reverse != 1) return set_err(PP_ERR_INVALID_ARGUMENT, "reverse is 0 or 1");
@@ -211,10 +210,9 @@ int pp_star_chain_segments(pp_ctx* ctx, const double* goals, const int64_t* coff
                            const int32_t* chain, int reverse, int64_t* off,
                            const pp_path_segments* seg, int64_t cap, int64_t* n_total,
                            double* length, uint8_t* ok) {
-    int r = check_ctx(ctx, true, false);
+    int r = star_ready(ctx);
     if (r) return r;
     StarBatch& s = ctx->star;
-    if (!s.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
     if (!goals || !coff || !off || !n_total)
         return set_err(PP_ERR_INVALID_ARGUMENT, "null goals, coff, off or n_total");
     if (reverse != 0 && reverse != 1) return set_err(PP_ERR_INVALID_ARGUMENT, "reverse is 0 or 1");
@@ -228,9 +226,8 @@ int pp_star_chain_segments(pp_ctx* ctx, const double* goals, const int64_t* coff
     if (nc > 0 && !chain) return set_err(PP_ERR_INVALID_ARGUMENT, "null chain");
     hipStream_t st = ctx->stream;
     // the chains against the trees as they are: every entry a node of its tree, the root last
-    std::vector<int> hn((size_t)Q);
-    PP_HIP(hipMemcpyAsync(hn.data(), s.f.n.p, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost, st));
-    PP_HIP(hipStreamSynchronize(st));
+    std::vector<int> hn;
+    if ((r = s.f.sizes(ctx, &hn))) return r;
     std::vector<int32_t> nodes((size_t)Q, -1);
     for (int q = 0; q < Q; ++q) {
         const int64_t c0 = coff[q], c1 = coff[q + 1];

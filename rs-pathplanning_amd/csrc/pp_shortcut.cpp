@@ -119,13 +119,6 @@ int shortcut_error(int err) {
     return PP_OK;
 }
 
-int star_ready(pp_ctx* ctx) {
-    int r = check_ctx(ctx, true, false);
-    if (r) return r;
-    if (!ctx->star.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
-    return PP_OK;
-}
-
 // ms (profiling, may be null): [0] chain + sizes, [1 .. 4] the rounds' emit / prep / walk / settle,
 // [5] the DP, [6] pack + copies; *rounds (may be null): the steer rounds
 int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int span, int64_t* off,
@@ -142,22 +135,13 @@ int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int sp
     for (int q = 0; q < Q; ++q)
         if (!finite3(goals + 3 * (size_t)q)) return set_err(PP_ERR_INVALID_ARGUMENT, "non-finite goal");
     hipStream_t st = ctx->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    std::vector<hipEvent_t> rev;
-    auto drop = [&]() {
-        for (hipEvent_t e : {e0, e1, e2, e3})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : rev) (void)hipEventDestroy(e);
-    };
+    Events ev;  // (profiling) [0 .. 3] the stages' marks, then 4 per round
     if (ms) {
-        for (hipEvent_t* e : {&e0, &e1, &e2, &e3}) PP_HIP(hipEventCreate(e));
-        PP_HIP(hipEventRecord(e0, st));
+        PP_HIP(ev.reserve(4));
+        PP_HIP(hipEventRecord(ev[0], st));
     }
     ScRun run;
-    if ((r = shortcut_sizes(ctx, goals, nodes, span, run))) {
-        drop();
-        return r;
-    }
+    if ((r = shortcut_sizes(ctx, goals, nodes, span, run))) return r;
     const int k = run.k;
     const double inf = std::numeric_limits<double>::infinity();
     *n_total = 0;
@@ -166,21 +150,16 @@ int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int sp
     if (ok) std::fill(ok, ok + Q, (uint8_t)0);
     if (n_tested) *n_tested = k ? run.pbase[(size_t)k] : 0;
     if (rounds) *rounds = run.rounds;
-    if (k == 0) {
-        drop();
-        return PP_OK;
-    }
+    if (k == 0) return PP_OK;
+    hipEvent_t* rev = nullptr;  // the rounds' events
     if (ms) {
-        rev.resize(4 * (size_t)run.rounds);
-        for (auto& e : rev) PP_HIP(hipEventCreate(&e));
-        PP_HIP(hipEventRecord(e1, st));
+        PP_HIP(ev.reserve(4 + 4 * (size_t)run.rounds));
+        rev = ev.data() + 4;
+        PP_HIP(hipEventRecord(ev[1], st));
     }
-    if ((r = shortcut_rounds(ctx, run, ms ? rev.data() : nullptr))) {
-        drop();
-        return r;
-    }
+    if ((r = shortcut_rounds(ctx, run, rev))) return r;
     PP_HIP(launch_shortcut_dp(st, run.a));
-    if (ms) PP_HIP(hipEventRecord(e2, st));
+    if (ms) PP_HIP(hipEventRecord(ev[2], st));
     std::vector<int> plen((size_t)k);
     std::vector<double> hc((size_t)k);
     int err = 0;
@@ -188,10 +167,7 @@ int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int sp
     PP_HIP(hipMemcpyAsync(hc.data(), sc.cost.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
     PP_HIP(hipMemcpyAsync(&err, sc.err.p, sizeof(int), hipMemcpyDeviceToHost, st));
     PP_HIP(hipStreamSynchronize(st));
-    if ((r = shortcut_error(err))) {
-        drop();
-        return r;
-    }
+    if ((r = shortcut_error(err))) return r;
     // the rows' offsets on the host (as pp_star_paths sizes its rows after one read-back)
     int64_t total = 0;
     for (int q = 0; q < Q; ++q) {
@@ -204,12 +180,9 @@ int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int sp
     }
     off[Q] = total;
     *n_total = total;
-    int rc = PP_OK;
     if (chain && cap > 0 && total > 0) {
-        if (cap < total) {
-            drop();
+        if (cap < total)
             return set_err(PP_ERR_CAPACITY, "chain smaller than the rows' total (n_total)");
-        }
         PP_HIP(sc.off.reserve((size_t)Q + 1));
         PP_HIP(sc.out.reserve((size_t)total));
         PP_HIP(hipMemcpyAsync(sc.off.p, off, ((size_t)Q + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -218,25 +191,25 @@ int star_shortcut(pp_ctx* ctx, const double* goals, const int32_t* nodes, int sp
         PP_HIP(hipStreamSynchronize(st));
     }
     if (ms) {
-        PP_HIP(hipEventRecord(e3, st));
-        PP_HIP(hipEventSynchronize(e3));
+        PP_HIP(hipEventRecord(ev[3], st));
+        PP_HIP(hipEventSynchronize(ev[3]));
         float f = 0.0f;
         for (int i = 0; i < 7; ++i) ms[i] = 0.0;
-        PP_HIP(hipEventElapsedTime(&f, e0, e1));
+        PP_HIP(hipEventElapsedTime(&f, ev[0], ev[1]));
         ms[0] = f;
-        for (int rd = 0; rd < run.rounds; ++rd)
-            for (int j = 0; j < 4; ++j) {
-                hipEvent_t from = j > 0 ? rev[4 * (size_t)rd + j - 1] : (rd > 0 ? rev[4 * (size_t)rd - 1] : e1);
-                PP_HIP(hipEventElapsedTime(&f, from, rev[4 * (size_t)rd + j]));
-                ms[1 + j] += f;
-            }
-        PP_HIP(hipEventElapsedTime(&f, run.rounds > 0 ? rev.back() : e1, e2));
+        // every round event's time since the one before it (the first round's: since ev[1])
+        hipEvent_t from = ev[1];
+        for (int i = 0; i < 4 * run.rounds; ++i) {
+            PP_HIP(hipEventElapsedTime(&f, from, rev[i]));
+            ms[1 + i % 4] += f;
+            from = rev[i];
+        }
+        PP_HIP(hipEventElapsedTime(&f, from, ev[2]));
         ms[5] = f;
-        PP_HIP(hipEventElapsedTime(&f, e2, e3));
+        PP_HIP(hipEventElapsedTime(&f, ev[2], ev[3]));
         ms[6] = f;
     }
-    drop();
-    return rc;
+    return PP_OK;
 }
 
 // pp_star_shortcut_commit.  ms (profiling, may be null): [0] chain + sizes, [1] the steer rounds,
@@ -254,20 +227,13 @@ int star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes,
     for (int q = 0; q < Q; ++q)
         if (!finite3(goals + 3 * (size_t)q)) return set_err(PP_ERR_INVALID_ARGUMENT, "non-finite goal");
     hipStream_t st = ctx->stream;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto drop = [&]() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    };
+    Events ev;  // (profiling) the marks between the stages
     if (ms) {
-        for (hipEvent_t& e : ev) PP_HIP(hipEventCreate(&e));
+        PP_HIP(ev.reserve(5));
         PP_HIP(hipEventRecord(ev[0], st));
     }
     ScRun run;
-    if ((r = shortcut_sizes(ctx, goals, nodes, span, run))) {
-        drop();
-        return r;
-    }
+    if ((r = shortcut_sizes(ctx, goals, nodes, span, run))) return r;
     const int k = run.k;
     if (node_out) std::fill(node_out, node_out + Q, (int32_t)-1);
     if (cost_out) std::fill(cost_out, cost_out + Q, std::numeric_limits<double>::infinity());
@@ -275,15 +241,9 @@ int star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes,
     if (n_tested) *n_tested = k ? run.pbase[(size_t)k] : 0;
     if (n_changed) *n_changed = 0;
     if (ms) std::fill(ms, ms + 4, 0.0);
-    if (k == 0) {
-        drop();
-        return PP_OK;
-    }
+    if (k == 0) return PP_OK;
     if (ms) PP_HIP(hipEventRecord(ev[1], st));
-    if ((r = shortcut_rounds(ctx, run))) {
-        drop();
-        return r;
-    }
+    if ((r = shortcut_rounds(ctx, run))) return r;
     if (ms) PP_HIP(hipEventRecord(ev[2], st));
     PP_HIP(sc.res.reserve(3 * (size_t)k));
     run.a.res = sc.res.p;
@@ -299,10 +259,7 @@ int star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes,
     PP_HIP(hipMemcpyAsync(&err, sc.err.p, sizeof(int), hipMemcpyDeviceToHost, st));
     if (ms) PP_HIP(hipEventRecord(ev[4], st));
     PP_HIP(hipStreamSynchronize(st));
-    if ((r = shortcut_error(err))) {
-        drop();
-        return r;
-    }
+    if ((r = shortcut_error(err))) return r;
     int64_t changed = 0;
     for (int q = 0; q < Q; ++q) {
         const int b = run.slot[(size_t)q];
@@ -320,7 +277,6 @@ int star_shortcut_commit(pp_ctx* ctx, const double* goals, const int32_t* nodes,
             ms[i] = f;
         }
     }
-    drop();
     return PP_OK;
 }
 

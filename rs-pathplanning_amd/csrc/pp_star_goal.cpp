@@ -8,13 +8,6 @@ using namespace ppamd;
 
 namespace {
 
-int star_ready(pp_ctx* ctx) {
-    int r = check_ctx(ctx, true, false);
-    if (r) return r;
-    if (!ctx->star.valid) return set_err(PP_ERR_STATE, "pp_star_new has not been called");
-    return PP_OK;
-}
-
 // a goal pose: finite, its position within PP_COORD_MAX
 bool finite3(const double* g) {
     return std::fabs(g[0]) <= PP_COORD_MAX && std::fabs(g[1]) <= PP_COORD_MAX && std::isfinite(g[2]);

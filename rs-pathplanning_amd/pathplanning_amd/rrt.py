@@ -476,6 +476,24 @@ class RRT:  # rrt.rs:325-620
         self.ctx.close()
 
 
+_I32P = C.POINTER(C.c_int32)
+
+
+def _compact_trees(ctx, q, n_old, fn, lead, n_counters):
+    """One call that compacts a forest's trees (revalidate, repair, advance, prune):
+    ``fn(ctx, *lead, n_nodes, <n_counters int64 counters>, new_index)``.  ``n_old``: the q old
+    sizes.  Returns (n_nodes int32[q] after the call, new_index int32[sum of the old sizes], the
+    counters)."""
+    n_old = np.asarray(n_old)
+    total = int(n_old.sum(dtype=np.int64))
+    new_index = np.zeros(max(total, 1), dtype=np.int32)
+    n = np.zeros(q, dtype=np.int32)
+    counters = [C.c_int64(0) for _ in range(n_counters)]
+    _ffi.check(fn(ctx.handle, *lead, n.ctypes.data_as(_I32P), *map(C.byref, counters),
+                  new_index.ctypes.data_as(_I32P)))
+    return n, new_index[:total], [c.value for c in counters]
+
+
 def _forest_slots(queries, q):
     """(slot array or None, its ctypes pointer or None, m) of an export / import call"""
     if queries is None:
@@ -697,15 +715,10 @@ class RRTBatch:
         after the call, new_index int32[sum of the old sizes]): query q's entries start at the
         prefix sum of the old sizes, each a node's index in its tree afterwards or -1.
         ``n_old``: the old sizes, for a batch whose scene was replaced behind its back."""
-        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
-        new_index = np.zeros(max(int(n_old.sum(dtype=np.int64)), 1), dtype=np.int32)
-        n = np.zeros(self.q, dtype=np.int32)
-        dropped = C.c_int64(0)
-        ip = C.POINTER(C.c_int32)
-        _ffi.check(_ffi.lib().pp_batch_revalidate(
-            self.ctx.handle, n.ctypes.data_as(ip), C.byref(dropped), new_index.ctypes.data_as(ip)))
-        self.last_dropped = dropped.value
-        return n, new_index[:int(n_old.sum(dtype=np.int64))]
+        n, new_index, (self.last_dropped,) = _compact_trees(
+            self.ctx, self.q, self.state()[0] if n_old is None else n_old,
+            _ffi.lib().pp_batch_revalidate, (), 1)
+        return n, new_index
 
     def set_space(self, space: Space):
         """Replace the scene of the batch and keep every tree where it still verifies."""
@@ -895,16 +908,10 @@ class RRTStarBatch:
         entries start at the prefix sum of the old sizes, each a node's index in its tree
         afterwards or -1.  ``n_old``: the old sizes, when already known.  ``last_dropped``: the
         nodes dropped over the batch."""
-        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
-        total = int(n_old.sum(dtype=np.int64))
-        new_index = np.zeros(max(total, 1), dtype=np.int32)
-        n = np.zeros(self.q, dtype=np.int32)
-        dropped = C.c_int64(0)
-        ip = C.POINTER(C.c_int32)
-        _ffi.check(_ffi.lib().pp_star_revalidate(
-            self.ctx.handle, n.ctypes.data_as(ip), C.byref(dropped), new_index.ctypes.data_as(ip)))
-        self.last_dropped = dropped.value
-        return n, new_index[:total]
+        n, new_index, (self.last_dropped,) = _compact_trees(
+            self.ctx, self.q, self.state()[0] if n_old is None else n_old,
+            _ffi.lib().pp_star_revalidate, (), 1)
+        return n, new_index
 
     def repair(self, rounds: int = 1, n_old=None):
         """``revalidate`` with up to ``rounds`` (0..16) re-attachment rounds (pp_star_repair): a
@@ -915,19 +922,10 @@ class RRTStarBatch:
         ``rounds = 0`` is ``revalidate``.  Returns (n_nodes, new_index) as ``revalidate`` does and
         sets ``last_dropped``, ``last_reattached`` (tops that found a parent) and
         ``last_recovered`` (nodes kept that ``revalidate`` would have dropped)."""
-        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
-        total = int(n_old.sum(dtype=np.int64))
-        new_index = np.zeros(max(total, 1), dtype=np.int32)
-        n = np.zeros(self.q, dtype=np.int32)
-        dropped, rea, rec = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        ip = C.POINTER(C.c_int32)
-        _ffi.check(_ffi.lib().pp_star_repair(
-            self.ctx.handle, int(rounds), n.ctypes.data_as(ip), C.byref(dropped), C.byref(rea),
-            C.byref(rec), new_index.ctypes.data_as(ip)))
-        self.last_dropped = dropped.value
-        self.last_reattached = rea.value
-        self.last_recovered = rec.value
-        return n, new_index[:total]
+        n, new_index, (self.last_dropped, self.last_reattached, self.last_recovered) = \
+            _compact_trees(self.ctx, self.q, self.state()[0] if n_old is None else n_old,
+                           _ffi.lib().pp_star_repair, (int(rounds),), 3)
+        return n, new_index
 
     def advance(self, nodes, hops=None, rounds: int = 0, n_old=None):
         """Move every query's root along its tree (pp_star_advance): the vehicle has driven, and
@@ -942,24 +940,16 @@ class RRTStarBatch:
         Counters, seeds and the focus stay (the old bound stays admissible; ``plan(goals,
         focus=True)`` tightens it).  Returns (n_nodes, new_index) as ``revalidate`` does and sets
         ``last_dropped``, ``last_reattached`` and ``last_recovered``."""
-        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
-        total = int(n_old.sum(dtype=np.int64))
-        new_index = np.zeros(max(total, 1), dtype=np.int32)
-        n = np.zeros(self.q, dtype=np.int32)
-        dropped, rea, rec = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        ip = C.POINTER(C.c_int32)
         nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(self.q)
         if hops is not None:
             hops = np.ascontiguousarray(np.broadcast_to(np.asarray(hops, dtype=np.int32),
                                                         (self.q,)))
-        _ffi.check(_ffi.lib().pp_star_advance(
-            self.ctx.handle, nodes.ctypes.data_as(ip),
-            None if hops is None else hops.ctypes.data_as(ip), int(rounds), n.ctypes.data_as(ip),
-            C.byref(dropped), C.byref(rea), C.byref(rec), new_index.ctypes.data_as(ip)))
-        self.last_dropped = dropped.value
-        self.last_reattached = rea.value
-        self.last_recovered = rec.value
-        return n, new_index[:total]
+        lead = (nodes.ctypes.data_as(_I32P), None if hops is None else hops.ctypes.data_as(_I32P),
+                int(rounds))
+        n, new_index, (self.last_dropped, self.last_reattached, self.last_recovered) = \
+            _compact_trees(self.ctx, self.q, self.state()[0] if n_old is None else n_old,
+                           _ffi.lib().pp_star_advance, lead, 3)
+        return n, new_index
 
     def set_space(self, space: Space, repair_rounds: int | None = None):
         """Replace the scene of the batch and keep every tree where it still holds: uploads
@@ -1016,19 +1006,12 @@ class RRTStarBatch:
         are remapped; the focus, counters and seeds stay.  Returns (n_nodes, new_index) as
         ``revalidate`` does and sets ``last_dropped``.  A node pruned now could have been made
         cheaper by a later rewire: the usual branch-and-bound trade."""
-        n_old = self.state()[0] if n_old is None else np.asarray(n_old)
-        total = int(n_old.sum(dtype=np.int64))
-        new_index = np.zeros(max(total, 1), dtype=np.int32)
-        n = np.zeros(self.q, dtype=np.int32)
-        dropped = C.c_int64(0)
-        ip = C.POINTER(C.c_int32)
         if keep is not None:
             keep = np.ascontiguousarray(keep, dtype=np.int32).reshape(self.q)
-        _ffi.check(_ffi.lib().pp_star_prune(
-            self.ctx.handle, None if keep is None else keep.ctypes.data_as(ip),
-            n.ctypes.data_as(ip), C.byref(dropped), new_index.ctypes.data_as(ip)))
-        self.last_dropped = dropped.value
-        return n, new_index[:total]
+        n, new_index, (self.last_dropped,) = _compact_trees(
+            self.ctx, self.q, self.state()[0] if n_old is None else n_old, _ffi.lib().pp_star_prune,
+            (None if keep is None else keep.ctypes.data_as(_I32P),), 1)
+        return n, new_index
 
     # ---- goal connection (pp_star_plan / pp_star_goal_costs / pp_star_path, DESIGN.md §3.7)
     def plan(self, goals, focus: bool = False, prune: bool = False, commit=None):

@@ -25,14 +25,14 @@ import pytest
 import star_goal_ref
 import star_revalidate_ref
 from scene_xform import moved
+from star_tree_cases import _set_space_checked
+from star_tree_cases import _trees as _star_trees
 from test_gpu_parity import ANG_TOL, PT_TOL, _assert_same_tree, _planner
 from test_gpu_rrtstar import COST_RTOL
 from test_gpu_rrtstar import _assert_same as _assert_same_star
 from test_gpu_rrtstar import _batch as _star_batch
 from test_gpu_rrtstar import _oracle as _star_oracle
 from test_gpu_star_repair import _repair_checked
-from test_gpu_star_revalidate import _prune_checked
-from test_gpu_star_revalidate import _trees as _star_trees
 
 pytestmark = pytest.mark.gpu
 
@@ -526,7 +526,7 @@ def test_rrtstar_scene_change_utm(pkg, ctx2, oracle_mod):
         # ---- one added disc: revalidate on a, repair(1) on the twin
         v = star_revalidate_ref.quarter_subtree_node(before[0])
         raw2 = star_revalidate_ref.with_discs(raw, [(before[0][0][v], before[0][1][v], 0.3)])
-        _, exp = _prune_checked(oracle_mod, a, before, raw2)
+        _, exp = _set_space_checked(oracle_mod, a, before, raw2)
         r = exp[0]
         assert not r["keep"][v] and 1 < r["kept"] < len(before[0][0]), r
         assert r["failed"] > 0 and r["orphans"] > 0, r

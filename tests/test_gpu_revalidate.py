@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import revalidate_ref as ref
+from star_tree_cases import _assert_exact, _space
 from test_gpu_parity import _assert_same_tree, _planner
 
 pytestmark = pytest.mark.gpu
@@ -22,22 +23,10 @@ def ctx(pkg):
     c.close()
 
 
-def _space(raw):
-    from pathplanning_amd import rrt
-
-    return rrt.Space.from_raw(raw)
-
-
 def _grown(pkg, raw, seed, n_iter, window=4096, ctx=None):
     p = _planner(pkg, raw, seed, window, ctx)
     p.extend(n_iter)
     return p, p.tree()
-
-
-def _assert_exact(got, exp):
-    for a, b in zip(got, exp):
-        assert len(a) == len(b), (len(a), len(b))
-        assert np.array_equal(a, b)
 
 
 def _revalidate_checked(oracle_mod, p, before, raw_new):

@@ -19,16 +19,14 @@ import star_advance_ref as adv
 import star_focus_ref
 import star_goal_ref
 import star_revalidate_ref as ref
+from star_tree_cases import (_assert_exact, _continue_checked, _space, _square, _starts, _trees,
+                             _with_ring)
 from test_gpu_rrtstar import COST_RTOL, _assert_same, _batch
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = [0, 5, 11, 12]
 CASES = [(0, 0.0), (0, 2.0), (4, 0.0), (8, 0.75)]
-
-
-def _starts(raw):
-    return [raw["start"], (-4.0, -4.5, 0.3), (-3.0, -3.0, 0.785), (2.0, -4.0, 1.2)]
 
 
 @pytest.fixture(scope="module")
@@ -38,26 +36,9 @@ def ctx(pkg):
     c.close()
 
 
-def _space(raw):
-    from pathplanning_amd import rrt
-
-    return rrt.Space.from_raw(raw)
-
-
-def _trees(b):
-    n = b.state()[0]
-    return [b.tree(q, n[q]) for q in range(b.q)]
-
-
 def _elens(st):
     off = st["off"]
     return [st["edge_cost"][off[q]:off[q + 1]] for q in range(len(off) - 1)]
-
-
-def _assert_exact(got, exp):
-    for a, e in zip(got, exp):
-        assert len(a) == len(e), (len(a), len(e))
-        assert np.array_equal(a, e)
 
 
 def _targets(osc, trees, goal, where):
@@ -131,31 +112,6 @@ def _advance_checked(b, osc, k, nodes, hops, rounds, check=None):
         assert np.allclose(cost[~k0], ecost[~k0], rtol=COST_RTOL, atol=0.0), q
         assert np.allclose(el1[~k0], e["elen"][~k0], rtol=COST_RTOL, atol=0.0), q
     return [exp[q] for q in range(b.q)] if check is None else exp
-
-
-def _continue_checked(oracle_mod, b, osc, exp, seeds, it0, n_steps, k, eta, queries=None):
-    """n_steps more lockstep steps against orc_star_extend continued from the restated trees
-    (`queries`: the ones compared; all)"""
-    rw0 = b.state()[3]
-    b.extend(n_steps)
-    n, it, _, rw = b.state()
-    assert (it == it0 + n_steps).all()
-    for q in (range(len(exp)) if queries is None else queries):
-        t = exp[q]["tree"]
-        tr = ref.oracle_tree((t[0][0], t[1][0], t[2][0]), t, exp[q]["elen"], n_steps)
-        _, erw, _, _ = oracle_mod.star_extend(osc, tr, int(seeds[q]), it0, n_steps, k, eta)
-        _assert_same(b.tree(q, n[q]), tr.star_arrays())
-        assert rw[q] - rw0[q] == erw, q
-
-
-def _with_ring(raw, ring):
-    out = dict(raw)
-    out["obstacle_polygons"] = list(raw["obstacle_polygons"]) + [np.asarray(ring, dtype=np.float64)]
-    return out
-
-
-def _square(cx, cy, half):
-    return np.array([(-half, -half), (half, -half), (half, half), (-half, half)]) + (cx, cy)
 
 
 # ------------------------------------------------------------- 1. identity and errors

@@ -21,9 +21,9 @@ import forest_state_ref
 import star_advance_ref as adv
 import star_focus_ref
 import star_revalidate_ref as ref
+from star_tree_cases import _continue_checked, _space, _square, _with_ring
 from test_gpu_rrtstar import _assert_same, _batch
-from test_gpu_star_advance import (_advance_checked, _continue_checked, _space, _square,
-                                    _with_ring)
+from test_gpu_star_advance import _advance_checked
 
 pytestmark = pytest.mark.gpu
 

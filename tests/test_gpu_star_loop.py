@@ -25,11 +25,12 @@ import pytest
 
 import forest_state_ref
 import star_loop_ref as loop
+from star_tree_cases import _space, _trees
 from test_gpu_rrtstar import COST_RTOL, _assert_same, _batch
 from test_gpu_star_advance import PER_SLOT, _advance_checked
 from test_gpu_star_goal import _check_query
 from test_gpu_star_prune import _prune_checked
-from test_gpu_star_repair import _repair_checked, _space, _trees
+from test_gpu_star_repair import _repair_checked
 from test_gpu_star_shortcut_commit import _check_exact, _commit
 
 pytestmark = pytest.mark.gpu

@@ -23,10 +23,9 @@ import pytest
 import star_focus_ref as focus_ref
 import star_prune_ref as ref
 import star_revalidate_ref as reval_ref
+from star_tree_cases import _assert_exact, _set_space_checked, _trees
 from test_gpu_rrtstar import _assert_same, _batch
 from test_gpu_star_focus import _check, _extend, _focus_refs, _plan_or, _refs, _set_focus
-from test_gpu_star_revalidate import _assert_exact, _trees
-from test_gpu_star_revalidate import _prune_checked as _set_space_checked
 from test_star_prune_ref import KETA, MARGIN, Q1_FACTOR
 
 pytestmark = pytest.mark.gpu

@@ -23,15 +23,13 @@ import revalidate_ref
 import star_goal_ref
 import star_repair_ref as rep
 import star_revalidate_ref as ref
-from test_gpu_rrtstar import COST_RTOL, _assert_same, _batch
+from star_tree_cases import (_assert_exact, _continue_checked, _space, _square, _starts, _trees,
+                             _with_ring)
+from test_gpu_rrtstar import COST_RTOL, _batch
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = [0, 5, 11, 12]
-
-
-def _starts(raw):
-    return [raw["start"], (-4.0, -4.5, 0.3), (-3.0, -3.0, 0.785), (2.0, -4.0, 1.2)]
 
 
 @pytest.fixture(scope="module")
@@ -39,23 +37,6 @@ def ctx(pkg):
     c = pkg.Context(0)
     yield c
     c.close()
-
-
-def _space(raw):
-    from pathplanning_amd import rrt
-
-    return rrt.Space.from_raw(raw)
-
-
-def _trees(b):
-    n = b.state()[0]
-    return [b.tree(q, n[q]) for q in range(b.q)]
-
-
-def _assert_exact(got, exp):
-    for a, e in zip(got, exp):
-        assert len(a) == len(e), (len(a), len(e))
-        assert np.array_equal(a, e)
 
 
 def _assert_tree(q, got, e):
@@ -95,31 +76,6 @@ def _repair_checked(oracle_mod, b, before, raw_new, k, rounds):
                                                            rep.min_gap(e))
         _assert_tree(q, b.tree(q, n_new[q]), e)
     return osc, exp
-
-
-def _continue_checked(oracle_mod, b, osc, exp, starts, seeds, it0, n_steps, k, eta, queries):
-    """n_steps more lockstep steps, then `queries` against orc_star_extend continued from the
-    restatement's repaired tree with its elen"""
-    rw0 = b.state()[3]
-    b.extend(n_steps)
-    n, it, _, rw = b.state()
-    assert (it == it0 + n_steps).all()
-    for q in queries:
-        e = exp[q]
-        tr = ref.oracle_tree(starts[q], e["tree"], e["elen"][e["keep"]], n_steps)
-        _, erw, _, _ = oracle_mod.star_extend(osc, tr, int(seeds[q]), it0, n_steps, k, eta)
-        _assert_same(b.tree(q, n[q]), tr.star_arrays())
-        assert rw[q] - rw0[q] == erw, q
-
-
-def _with_ring(raw, ring):
-    out = dict(raw)
-    out["obstacle_polygons"] = list(raw["obstacle_polygons"]) + [np.asarray(ring, dtype=np.float64)]
-    return out
-
-
-def _square(cx, cy, half):
-    return np.array([(-half, -half), (half, -half), (half, half), (-half, half)]) + (cx, cy)
 
 
 # ------------------------------------------- 1. rounds = 0, and the unchanged scene
@@ -183,7 +139,7 @@ def test_one_disc_then_continue(pkg, ctx, oracle_mod, k, eta, rounds):
         assert r["recovered"] >= 30, r["rounds"]
         assert r["recovered"] - r["reattached"] > r["reattached"], r["rounds"]
         later += sum(d["reattached"] for d in r["rounds"][1:])
-        _continue_checked(oracle_mod, b, osc2, exp, starts, SEEDS, n1, n2, k, eta, range(4))
+        _continue_checked(oracle_mod, b, osc2, exp, SEEDS, n1, n2, k, eta, range(4))
         # the goal connection on the repaired-and-extended trees, in the new scene
         after = _trees(b)
         node, cost = b.plan(goal)
@@ -221,7 +177,7 @@ def test_field512_trees_under_the_grid(pkg, ctx, oracle_mod):
     r = exp[2]
     assert r["keep0"].sum() == 1 and len(before[2][0]) > 100
     assert r["rounds"][0]["tasks"] == r["rounds"][0]["tops"] > 0
-    _continue_checked(oracle_mod, b, osc2, exp, [tuple(s) for s in starts], seeds, n1, n2, 0, eta,
+    _continue_checked(oracle_mod, b, osc2, exp, seeds, n1, n2, 0, eta,
                       range(4))
 
 
@@ -269,7 +225,7 @@ def test_root_inside_a_polygon(pkg, ctx, oracle_mod):
     osc2, exp = _repair_checked(oracle_mod, b, before, full, 0, 3)
     assert exp[0]["kept"] == 1 and exp[0]["rounds"] == [] and exp[1]["kept"] > 1
     rw0 = b.state()[3]
-    _continue_checked(oracle_mod, b, osc2, exp, starts, seeds, 400, 100, 0, 0.0, [1])
+    _continue_checked(oracle_mod, b, osc2, exp, seeds, 400, 100, 0, 0.0, [1])
     n, it, _, rw = b.state()
     assert n[0] == 1 and it[0] == 500 and rw[0] == rw0[0]
     _assert_exact(b.tree(0, 1), [a[:1] for a in before[0]])
@@ -306,7 +262,7 @@ def test_more_than_two_steer_slices(pkg, ctx, oracle_mod):
     cum = np.cumsum(tops)
     edge = [int(np.searchsorted(cum, t, side="right")) for t in (512, 1024)]
     none = int(np.flatnonzero(tops == 0)[0])
-    _continue_checked(oracle_mod, b, osc2, exp, [tuple(s) for s in starts], seeds, n1, n2, 0, 0.0,
+    _continue_checked(oracle_mod, b, osc2, exp, seeds, n1, n2, 0, 0.0,
                       sorted(set([0, Q - 1, none] + edge)))
 
 

@@ -15,15 +15,13 @@ import pytest
 import revalidate_ref
 import star_goal_ref
 import star_revalidate_ref as ref
-from test_gpu_rrtstar import _assert_same, _batch
+from star_tree_cases import (_assert_exact, _continue_checked, _set_space_checked, _space, _square,
+                             _starts, _trees, _with_ring)
+from test_gpu_rrtstar import _batch
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = [0, 5, 11, 12]
-
-
-def _starts(raw):
-    return [raw["start"], (-4.0, -4.5, 0.3), (-3.0, -3.0, 0.785), (2.0, -4.0, 1.2)]
 
 
 @pytest.fixture(scope="module")
@@ -31,72 +29,6 @@ def ctx(pkg):
     c = pkg.Context(0)
     yield c
     c.close()
-
-
-def _space(raw):
-    from pathplanning_amd import rrt
-
-    return rrt.Space.from_raw(raw)
-
-
-def _trees(b):
-    n = b.state()[0]
-    return [b.tree(q, n[q]) for q in range(b.q)]
-
-
-def _assert_exact(got, exp):
-    for a, e in zip(got, exp):
-        assert len(a) == len(e), (len(a), len(e))
-        assert np.array_equal(a, e)
-
-
-def _prune_checked(oracle_mod, b, before, raw_new):
-    """set_space(raw_new) on batch b holding the trees `before`; everything the call returns and
-    leaves behind against the restatement.  Returns (the new scene, the restatements)."""
-    osc = oracle_mod.OracleScene.from_raw(raw_new)
-    exp = [ref.revalidate(osc, t) for t in before]
-    assert sum(e["none_edges"] for e in exp) == 0
-    n_old = np.array([len(t[0]) for t in before])
-    _, it_old, ev_old, rw_old = b.state()
-    n_new, new_index = b.set_space(_space(raw_new))
-    off = np.concatenate([[0], np.cumsum(n_old)])
-    assert len(new_index) == off[-1]
-    assert np.array_equal(n_new, [e["kept"] for e in exp])
-    assert b.last_dropped == int((n_old - n_new).sum())
-    n_state, it, ev, rw = b.state()
-    assert np.array_equal(n_state, n_new)
-    assert np.array_equal(it, it_old) and np.array_equal(ev, ev_old) and np.array_equal(rw, rw_old)
-    for q, e in enumerate(exp):
-        got_index = new_index[off[q]:off[q + 1]]
-        assert np.array_equal(got_index, e["new_index"]), (q, np.flatnonzero(got_index != e["new_index"])[:10])
-        # x, y, yaw, the remapped parents, and the cost of the export before the call, bit for bit
-        _assert_exact(b.tree(q, n_new[q]), e["tree"])
-    return osc, exp
-
-
-def _continue_checked(oracle_mod, b, osc, exp, starts, seeds, it0, n_steps, k, eta, queries):
-    """n_steps more lockstep steps, then `queries` against orc_star_extend continued from the
-    pruned tree: rows from the restatement, cost from the export, elen from the restatement"""
-    rw0 = b.state()[3]
-    b.extend(n_steps)
-    n, it, _, rw = b.state()
-    assert (it == it0 + n_steps).all()
-    for q in queries:
-        e = exp[q]
-        tr = ref.oracle_tree(starts[q], e["tree"], e["elen"][e["keep"]], n_steps)
-        _, erw, _, _ = oracle_mod.star_extend(osc, tr, int(seeds[q]), it0, n_steps, k, eta)
-        _assert_same(b.tree(q, n[q]), tr.star_arrays())
-        assert rw[q] - rw0[q] == erw, q
-
-
-def _with_ring(raw, ring):
-    out = dict(raw)
-    out["obstacle_polygons"] = list(raw["obstacle_polygons"]) + [np.asarray(ring, dtype=np.float64)]
-    return out
-
-
-def _square(cx, cy, half):
-    return np.array([(-half, -half), (half, -half), (half, half), (-half, half)]) + (cx, cy)
 
 
 # ------------------------------------------------------------------ 1. the unchanged scene
@@ -149,12 +81,12 @@ def test_one_disc_then_continue(pkg, ctx, oracle_mod, k, eta):
         before = _trees(b)
         v = ref.quarter_subtree_node(before[j])
         raw2 = ref.with_discs(raw, [(before[j][0][v], before[j][1][v], 0.3)])
-        osc2, exp = _prune_checked(oracle_mod, b, before, raw2)
+        osc2, exp = _set_space_checked(oracle_mod, b, before, raw2)
         r = exp[j]
         assert not r["keep"][v] and 1 < r["kept"] < len(before[j][0]), r
         assert r["failed"] > 0 and r["orphans"] > 0, r
         assert r["kept_back"] > 0 and r["orphans_via_later"] > 0, r
-        _continue_checked(oracle_mod, b, osc2, exp, starts, SEEDS, n1, n2, k, eta, range(4))
+        _continue_checked(oracle_mod, b, osc2, exp, SEEDS, n1, n2, k, eta, range(4))
         # the goal connection on the pruned-and-extended trees, in the new scene
         after = _trees(b)
         node, cost = b.plan(goal)
@@ -181,13 +113,13 @@ def test_field512_trees_under_the_grid(pkg, ctx, oracle_mod):
     b = _batch(pkg, raw, starts, seeds, n1 + n2, 0, eta, ctx=ctx)
     b.extend(n1)
     before = _trees(b)
-    osc2, exp = _prune_checked(oracle_mod, b, before, scenes.field512_grid())
+    osc2, exp = _set_space_checked(oracle_mod, b, before, scenes.field512_grid())
     for q in (0, 1):
         r = exp[q]
         assert 1 < r["kept"] < len(before[q][0]), (q, r)
         assert r["kept_back"] > 0 and r["orphans_via_later"] > 0, (q, r)
     assert exp[2]["kept"] == 1 and len(before[2][0]) > 100  # only its root stays
-    _continue_checked(oracle_mod, b, osc2, exp, [tuple(s) for s in starts], seeds, n1, n2, 0, eta,
+    _continue_checked(oracle_mod, b, osc2, exp, seeds, n1, n2, 0, eta,
                       range(4))
 
 
@@ -204,7 +136,7 @@ def test_polygons_with_an_added_ring(pkg, ctx, oracle_mod):
         before = _trees(b)
         v = ref.quarter_subtree_node(before[j])
         raw2 = _with_ring(raw, _square(before[j][0][v], before[j][1][v], 0.5))
-        _, exp = _prune_checked(oracle_mod, b, before, raw2)
+        _, exp = _set_space_checked(oracle_mod, b, before, raw2)
         r = exp[j]
         assert not r["keep"][v] and 1 < r["kept"] < len(before[j][0]), r
         assert r["orphans"] > 0 and r["kept_back"] > 0 and r["orphans_via_later"] > 0, r
@@ -231,10 +163,10 @@ def test_root_inside_a_polygon(pkg, ctx, oracle_mod):
     before = _trees(b)
     par = before[0][3]
     assert len(par) > 100 and (par[1:] > np.arange(1, len(par))).sum() > 10
-    osc2, exp = _prune_checked(oracle_mod, b, before, full)
+    osc2, exp = _set_space_checked(oracle_mod, b, before, full)
     assert exp[0]["kept"] == 1 and exp[1]["kept"] > 1
     rw0 = b.state()[3]
-    _continue_checked(oracle_mod, b, osc2, exp, starts, seeds, 400, 100, 0, 0.0, [1])
+    _continue_checked(oracle_mod, b, osc2, exp, seeds, 400, 100, 0, 0.0, [1])
     n, it, _, rw = b.state()
     assert n[0] == 1 and it[0] == 500 and rw[0] == rw0[0]
     _assert_exact(b.tree(0, 1), [a[:1] for a in before[0]])
@@ -263,7 +195,7 @@ def test_three_slices_two_sub_batches(pkg, ctx, oracle_mod):
         cx = rng.uniform(xs.min(), xs.max())
         cy = rng.uniform(ys.min(), ys.max())
         discs.append((cx, cy, rng.uniform(0.3, 0.8)))
-    osc2, exp = _prune_checked(oracle_mod, b, before, ref.with_discs(raw, discs))
+    osc2, exp = _set_space_checked(oracle_mod, b, before, ref.with_discs(raw, discs))
     # the queries that hold the global nodes at which the steer slices change
     straddle = [int(np.searchsorted(off, g, side="right") - 1) for g in (32768, 65536)]
     for q, g in zip(straddle, (32768, 65536)):
@@ -274,7 +206,7 @@ def test_three_slices_two_sub_batches(pkg, ctx, oracle_mod):
     assert dropped.min() == 0 < dropped.max()
     assert sum(e["orphans"] for e in exp) > 0 and sum(e["kept_back"] for e in exp) > 0
     assert sum(e["orphans_via_later"] for e in exp) > 0
-    _continue_checked(oracle_mod, b, osc2, exp, [tuple(s) for s in starts], seeds, n1, n2, 0, 0.0,
+    _continue_checked(oracle_mod, b, osc2, exp, seeds, n1, n2, 0, 0.0,
                       [0, 159, 160, Q - 1] + straddle)
 
 
