@@ -57,7 +57,9 @@ extern "C" {
  * 5 (+): pp_star_shortcut_commit added (the chain's shortcuts written back into the RRT* trees as
  *        rewires), nothing else changed
  * 5 (+): pp_star_advance added (a node of every RRT* tree becomes its root; what hung from its
- *        ancestors is re-attached by pp_star_repair's rounds), nothing else changed */
+ *        ancestors is re-attached by pp_star_repair's rounds), nothing else changed
+ * 5 (+): pp_star_relax added, nothing else changed (every node of the RRT* trees looks for a
+ *        cheaper parent in its own tree; pp_star_relax_counts reads its profiling counters) */
 #define PP_ABI_VERSION 5
 
 #define PP_OK 0
@@ -601,6 +603,68 @@ int pp_star_repair(pp_ctx* ctx, int rounds, int32_t* n_nodes, int64_t* n_dropped
 int pp_star_advance(pp_ctx* ctx, const int32_t* nodes, const int32_t* hops, int rounds,
                     int32_t* n_nodes, int64_t* n_dropped, int64_t* n_reattached,
                     int64_t* n_recovered, int32_t* new_index);
+/* Relax the trees of the RRT* batch (build-defined, DESIGN.md §3.8 "Relaxing the trees"; CPU
+ * restatement tests/star_relax_ref.py): up to `rounds` in [1, 16] synchronous choose-parent rounds
+ * over all nodes, on the device and in place.  It is pp_star_repair's choose-parent pass with
+ * every node a top: nothing else in the library lets existing nodes look for a cheaper parent
+ * among existing nodes (RT-RRT*'s rewiring from the root, RRT#'s relaxation).  All quantities are
+ * build-defined and follow §3.7's conventions.
+ *
+ * One query q with active[q] != 0 (active NULL: all), n its tree size, the context's current
+ * Space, the batch's k.  An inactive query, a tree of one node and a root-blocked query are
+ * untouched bit for bit.  A round reads parent, cost and edge cost as they stood when it began:
+ *
+ * Candidates.  The candidates of node i > 0 are the star_k(k, n - 1) nearest nodes j != i of its
+ * tree by exact f64 (dx * dx + dy * dy, index).  The root is a candidate like any other.  The
+ * candidate equal to parent[i] keeps its place in the order but is never evaluated: by the cost
+ * invariant its total is the node's own cost, and deriving it again through another math library
+ * would turn an exact tie into a coin toss.
+ *
+ * Edge.  The edge i -> p keeps i's stored pose, yaw included (like a rewire or a repair top), and
+ * runs to p's stored pose; it is feasible when the word is Some and Space::verify accepts its
+ * points followed by p's point.  total = cost[p] + e, one rounded f64 add.
+ *
+ * Choice.  The first strict minimum of total in candidate order among the feasible candidates,
+ * accepted only when total < cost[i] (strict, the extend's own rewire test).  A node with a choice
+ * stages parent = p and edge cost = e; no node reads another node's staged values, so the order
+ * in which nodes are taken cannot matter.
+ *
+ * Apply and rebuild.  After every node has chosen, the staged parents and edge costs are applied
+ * and cost is rebuilt from the root level by level, cost[i] = cost[parent[i]] + elen[i], parents
+ * final before children (pp_star_advance's order of additions, never a prefix sum): the invariant
+ * pp_star_forest_import checks holds bit for bit.  No cycle can form: a new edge i -> p has
+ * cost[p] + e < cost[i] with e >= 0, a stored edge has cost[parent] <= cost[child], so a cycle
+ * would need start-of-round costs that never rise around it, hence no new edge on it.  No cost
+ * rises (induction from the root, a rounded add is monotone), and a node with no re-parented
+ * ancestor-or-self keeps its cost bit for bit.
+ *
+ * Early stop.  A round that re-parents nothing in any active query ends the call; *rounds_run
+ * (may be NULL) counts the rounds executed, that last one included.  A call that ended so,
+ * repeated, runs one round and changes nothing; so does a call in which no query takes part
+ * (all inactive, root-blocked or lone roots): one round, nothing changed.
+ *
+ * n_rewired[q] (may be NULL): the re-parentings of query q over all rounds; the query's rewire
+ * counter of pp_star_state advances by it, as pp_star_shortcut_commit's does.  *n_changed (may be
+ * NULL): the nodes over the batch whose cost differs bit-wise from before the call.
+ *
+ * Untouched: poses, node order, tree sizes, iterations, seeds, skipped draws, the focus and its
+ * bound (it stays admissible: costs only fall), node_evals, pp_stats and the blocked flags.  The
+ * call neither verifies nor un-verifies a stored edge: on a tree that was not revalidated after a
+ * scene change it may hang a node under one whose own chain no longer holds.
+ *
+ * PP_ERR_STATE without an RRT* batch or a scene, PP_ERR_INVALID_ARGUMENT for a NULL ctx or rounds
+ * outside [1, 16], checked on the host before anything is launched.  PP_ERR_STEER_OVERFLOW: the
+ * failing round is not applied, the rounds before it stay (each leaves a valid tree), *rounds_run
+ * says how many were applied and n_rewired / *n_changed describe them.  The host synchronises to
+ * read the sizes, once per round run, and once at the end. */
+int pp_star_relax(pp_ctx* ctx, int rounds, const uint8_t* active, int32_t* n_rewired,
+                  int32_t* rounds_run, int64_t* n_changed);
+/* The last pp_star_relax call's counters, summed over its rounds: out[0] nodes of the forest,
+ * out[1] candidates of the nodes that took part, out[2] those left after the parent skip, out[3]
+ * after the skip of cost[p] >= cost[i], out[4] after the chord bound (the steer tasks), out[5] the
+ * tasks whose edge was walked, out[6] node slices per round, out[7] the largest candidate count.
+ * out[1 .. 5] are collected only while profiling is on (pp_set_profiling) and are 0 otherwise. */
+int pp_star_relax_counts(pp_ctx* ctx, int64_t out[8]);
 /* Goal connection (build-defined; CPU restatement tests/star_goal_ref.py).  The
  * goal edge of tree node m: the goal (gx, gy, gyaw) is the child and keeps its yaw, node m is the
  * parent — Dubins from the goal pose to the node's stored pose; feasible when the word is Some and

@@ -322,9 +322,11 @@ int mq_reserve_tasks(pp_ctx* c, int q, int K) {
     return PP_OK;
 }
 
+}  // namespace
+
 // |X_near| of an insert into an n-node RRT* tree: k_fixed, or the k-nearest RRT* schedule
 // ceil(2e ln n) (Karaman & Frazzoli), capped at kStarKMax and at n (orc_star_k restates it)
-int star_k(int k_fixed, int n) {
+int ppamd::star_k(int k_fixed, int n) {
     int k;
     if (k_fixed > 0) {
         k = k_fixed;
@@ -335,8 +337,6 @@ int star_k(int k_fixed, int n) {
     if (k > kStarKMax) k = kStarKMax;
     return k < n ? k : n;
 }
-
-}  // namespace
 
 StarArgs ppamd::star_args(pp_ctx* c) {
     const StarBatch& s = c->star;

@@ -11,6 +11,7 @@
 //                      pp_star_revalidate
 //   pp_repair.cpp   the re-attachment rounds: pp_star_repair (that revalidation with the rounds) and
 //                   pp_star_advance (a node becomes the root; the rounds on its ancestors)
+//   pp_relax.cpp    pp_star_relax: choose-parent rounds over every node of the RRT* trees
 //   pp_prune.cpp    pp_star_prune: its doubling and compaction behind the focus bound's verdicts
 //   pp_forest_io.cpp  pp_star_forest_export / _import, pp_batch_forest_export / _import
 //   pp_segments.cpp  pp_star_path_segments, pp_batch_path_segments, pp_star_chain_segments,
@@ -464,8 +465,14 @@ struct Reval {
     DBuf<int> lvl, wpar, tops, tslot, tcnt, near;
     DBuf<double> wcost, welen, tcost;
     DBuf<RepairRec> rrec;
-    // pp_star_prune (PruneArgs); pp_star_advance's nodes, hops and roots (AdvanceArgs)
+    // pp_star_prune (PruneArgs); pp_star_advance's nodes, hops and roots (AdvanceArgs);
+    // pp_star_relax's per-query rewires
     DBuf<int> keep;
+    // pp_star_relax (RelaxArgs): its counters, and the last call's for pp_star_relax_counts; its
+    // other buffers are the repair's (tasks .. yaw, tcost, tslot, tcnt, wpar, welen, lvl; flag:
+    // the changed costs; qhas: the active queries)
+    DBuf<RelaxRec> relax_rec;
+    int64_t relax_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // ---- packed forest export / import (pp_*_forest_export / pp_*_forest_import: ForestIoArgs), sized
@@ -584,6 +591,8 @@ int ensure_events(pp_ctx* c, size_t count);
 int ensure_literal_pool(pp_ctx* c, hipStream_t st);
 // the RRT* batch's kernel arguments, the whole batch's view (pp_batch.cpp)
 StarArgs star_args(pp_ctx* c);
+// |X_near| of an insert into an n-node RRT* tree (pp_batch.cpp; the batch's ksched[] holds it)
+int star_k(int k_fixed, int n);
 // The steps pp_batch_paths and pp_star_paths share (pp_finish.cpp).  paths_items: the call's
 // (query, node) items from nodes[0, Q) (-1: skipped; sizes: the trees' node counts) into
 // paths.qidx / nodes / slot on the device, *k their count.  paths_sizes: the rows' offsets from

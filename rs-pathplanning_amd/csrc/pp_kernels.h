@@ -534,6 +534,66 @@ enum : int { kAdvanceCore = 0, kAdvanceTops, kAdvanceKeep, kAdvanceGather, kAdva
 // steer overflowed)
 hipError_t launch_advance_stage(hipStream_t s, const AdvanceArgs& a, int stage, int passes);
 
+// Relax (pp_star_relax, pp_k_relax.hip; DESIGN.md §3.8 "Relaxing the trees"): every node of an
+// RRT* forest looks for a cheaper parent among the nodes of its own tree, in synchronous rounds.
+// Node g of the `total` nodes is node g - off[q] of tree q, as in RevalArgs; arrays marked [total]
+// are indexed by g.  Nothing is sized by nodes x candidates: a slice of nodes packs its steer tasks
+// straight from the kNN.
+constexpr int kRelaxMaxRounds = 16;
+constexpr int kRelaxNodesPerSlice = 16384;  // <= 16384 * star_k tasks a steer slice
+struct RelaxRec {  // the counters the host reads
+    int rewired;        // re-parentings so far, all rounds
+    int pad;
+    long long changed;  // nodes whose cost differs from before the call
+    // profiling only (RelaxArgs::stats): candidates of the live nodes, those left after the parent
+    // skip, after the cost skip, after the chord bound (the steer tasks), and the tasks walked
+    long long cand, not_parent, cheaper, tasks, walked;
+};
+struct RelaxArgs {
+    TreeDev tr{};
+    int Q = 0;
+    size_t cap = 0;
+    const int* off = nullptr;          // [Q + 1] exclusive scan of the trees' node counts
+    int total = 0;                     // off[Q]
+    const uint8_t* blocked = nullptr;  // [Q] the root fails verify: the query stays (may be null)
+    const uint8_t* active = nullptr;   // [Q] 0: the query stays (null: every query takes part)
+    double* cost = nullptr;            // the batch's rows
+    double* elen = nullptr;
+    int64_t* rewires = nullptr;        // [Q] the batch's rewire counters
+    const int* ksched = nullptr;       // [cap + 1] star_k of the batch
+    double curv = 0.0;                 // 1 / turn radius: the chord lower bound of a Dubins cost
+    int kmax = 0;                      // the most candidates a node of this forest has
+    // one slice of steer tasks at a time
+    int task_cap = 0;                  // >= the largest slice's nodes * kmax
+    SteerTask* tasks = nullptr;
+    StarTaskExt* ext = nullptr;
+    PrepRec* rec = nullptr;
+    int* status = nullptr;
+    double* yaw = nullptr;
+    double* tcost = nullptr;           // the Dubins cost of each task
+    DevState* st = nullptr;
+    int* tslot = nullptr;              // [kRelaxNodesPerSlice] first task of a slice's node
+    int* tcnt = nullptr;               // [kRelaxNodesPerSlice] ... and their count
+    int* wpar = nullptr;               // [total] the round's staged parent, -1: the node stays
+    double* welen = nullptr;           // [total] ... and its edge cost
+    int* lvl = nullptr;                // [total] the commit's levels
+    unsigned char* chg = nullptr;      // [total] the node's cost moved in this call
+    int* nrw = nullptr;                // [Q] the call's re-parentings per query
+    RelaxRec* rrec = nullptr;
+    int stats = 0;                     // collect rrec's profiling counters
+    int* err = nullptr;                // != 0: a steer overflowed n_point; the round is not applied
+    double* lit_scratch = nullptr;     // kLiteralWaves buffers
+    int* lit_locks = nullptr;
+    long long* wg_points = nullptr;    // profiling: walked points per walk workgroup (or null)
+};
+// the steer round of the nodes [g0, g1), g1 - g0 <= kRelaxNodesPerSlice: the self-join kNN with
+// its culls and tasks, prep, walk, choose (the staged rows)
+hipError_t launch_relax_slice(hipStream_t s, const SceneDev& sc, const RelaxArgs& a, int g0,
+                              int g1);
+// after a round's last slice: the staged rows into the trees unless a steer overflowed, the costs
+// rebuilt from the root level by level, the counters
+hipError_t launch_relax_commit(hipStream_t s, const RelaxArgs& a);
+
 // Prune (pp_star_prune, pp_k_prune.hip; DESIGN.md §3.7 "Pruning by the focus bound"): the keep
 // words of an RRT* forest by its queries' focus bounds, in front of launch_reval_jump and
 // launch_reval_compact.  No steer: rv's slice buffers are unused.

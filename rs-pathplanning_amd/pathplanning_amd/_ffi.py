@@ -48,7 +48,8 @@ EXPORTED = [
     "pp_batch_plan", "pp_batch_paths",
     "pp_rrt_revalidate", "pp_batch_revalidate",
     "pp_star_new", "pp_star_extend", "pp_star_state", "pp_star_tree_export", "pp_star_revalidate",
-    "pp_star_repair", "pp_star_advance", "pp_star_set_focus", "pp_star_get_focus", "pp_star_prune",
+    "pp_star_repair", "pp_star_advance", "pp_star_relax", "pp_star_relax_counts",
+    "pp_star_set_focus", "pp_star_get_focus", "pp_star_prune",
     "pp_star_plan", "pp_star_goal_costs", "pp_star_path", "pp_star_paths",
     "pp_star_path_segments", "pp_batch_path_segments", "pp_segments_sample",
     "pp_star_shortcut", "pp_star_shortcut_edges", "pp_star_chain_segments",
@@ -222,6 +223,8 @@ def lib():
             "pp_star_revalidate": ([vp, ip, i64p, ip], C.c_int),
             "pp_star_repair": ([vp, C.c_int, ip, i64p, i64p, i64p, ip], C.c_int),
             "pp_star_advance": ([vp, ip, ip, C.c_int, ip, i64p, i64p, i64p, ip], C.c_int),
+            "pp_star_relax": ([vp, C.c_int, C.POINTER(C.c_uint8), ip, ip, i64p], C.c_int),
+            "pp_star_relax_counts": ([vp, i64p], C.c_int),
             "pp_star_set_focus": ([vp, dp, dp], C.c_int),
             "pp_star_get_focus": ([vp, dp, dp, i64p], C.c_int),
             "pp_star_prune": ([vp, ip, ip, i64p, ip], C.c_int),

@@ -951,6 +951,40 @@ class RRTStarBatch:
                            _ffi.lib().pp_star_advance, lead, 3)
         return n, new_index
 
+    def relax(self, rounds: int = 1, active=None):
+        """Let every node of every tree look for a cheaper parent among the nodes of its own tree
+        (pp_star_relax): up to ``rounds`` (1..16) synchronous choose-parent rounds, on the device
+        and in place.  A node's candidates are its star_k nearest other nodes; the edge keeps the
+        node's pose, like a rewire; the first strict minimum of cost[parent] + edge cost wins when
+        it is strictly below the node's cost; after every node has chosen, the costs are rebuilt
+        from the root.  A round that re-parents nothing ends the call.  ``active`` (None: all):
+        one flag per query, 0 leaves the query untouched.  Poses, node order, sizes and every
+        counter but ``rewires`` stay; no cost rises, so a focus bound stays admissible.  The call
+        is what follows ``advance``: the trees that survived hang by detours until their nodes
+        have looked around.  Returns n_rewired int32[q] and sets ``last_rounds`` (the rounds run)
+        and ``last_changed`` (the nodes whose cost changed)."""
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active).reshape(self.q) != 0, dtype=np.uint8)
+        nrw = np.zeros(self.q, dtype=np.int32)
+        run, changed = C.c_int32(0), C.c_int64(0)
+        _ffi.check(_ffi.lib().pp_star_relax(
+            self.ctx.handle, int(rounds),
+            None if act is None else act.ctypes.data_as(C.POINTER(C.c_uint8)),
+            nrw.ctypes.data_as(_I32P), C.byref(run), C.byref(changed)))
+        self.last_rounds = run.value
+        self.last_changed = changed.value
+        return nrw
+
+    def relax_counts(self) -> dict:
+        """The last ``relax`` call's profiling counters (pp_star_relax_counts; all but ``nodes``,
+        ``slices`` and ``kmax`` are zero unless ``set_profiling(True)``)."""
+        v = np.zeros(8, dtype=np.int64)
+        _ffi.check(_ffi.lib().pp_star_relax_counts(self.ctx.handle,
+                                                   v.ctypes.data_as(C.POINTER(C.c_int64))))
+        keys = ("nodes", "candidates", "not_parent", "cheaper", "tasks", "walked", "slices", "kmax")
+        return dict(zip(keys, (int(a) for a in v)))
+
     def set_space(self, space: Space, repair_rounds: int | None = None):
         """Replace the scene of the batch and keep every tree where it still holds: uploads
         ``space`` into the batch's context and revalidates — with ``repair_rounds`` given, by
